@@ -6,7 +6,7 @@ One "step" = one rollout = one PILCO.predict(m0, S0, H=40) (pilco.py:118-136) wi
 the GP factorisation cached on the device ("R-fwd" of SURVEY.md 8(d)); inputs are
 resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: launched under torch.distributed.run, one rank per GPU.  torch is used only
 to rendezvous (gloo: broadcast of the RCCL unique id and of the peer-exchange
@@ -452,6 +452,14 @@ def verify_against_reference(mH, SH, reward, fatal=True):
     return dict(against="tests/golden/c2_rollout.npz (reference source executed, H=40)", rtol=1e-5, max_rel_err=errs)
 
 
+def dump_outputs(out_dir, mH, SH, reward):
+    """What the last timed step's pilco_rollout call handed its caller, unchanged (float64): m_H (1, E), S_H (E, E) and
+    the reward (1, 1).  The inputs are fixed (synthetic.config_c2, seed 1234), so two builds compare output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("m_H", mH), ("S_H", SH), ("reward", reward)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -459,7 +467,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (m_H, S_H, reward; float64) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -467,15 +479,17 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Invoked plainly (`python bench.py --gpus N ...`, the way the driver types the 1-GPU line): start the N ranks
         # ourselves -- the same launcher line the driver uses, one process per GPU, rendezvous on 127.0.0.1 -- and let
-        # rank 0 of that job print the one JSON line.  exec, not spawn: no second Python sits above the ranks.
+        # rank 0 of that job print the one JSON line.  The launcher runs as a child (this process never touches a GPU)
+        # and its exit status is ours.
         import socket
+        import subprocess
         with socket.socket() as so:
             so.bind(("127.0.0.1", 0))
             port = so.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(sys.argv[0])] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        raise SystemExit(subprocess.call(cmd))
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d (launch one rank per GPU, or call it without a launcher)"
                          % (args.gpus, world))
@@ -592,6 +606,8 @@ def main():
     wall_ms, per_call, (mH, SH, rew) = timed_leg()
     ms_per_rollout = wall_ms / args.steps
     verified = verify_against_reference(mH, SH, float(rew[0, 0])) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mH, SH, rew)
 
     # dominant kernel (pair kernel): its own HIP-event pairs on the launch stream, separate pass
     prof = ctx.rollout_timed(policy, rewards, cfg["m0"], cfg["S0"], H, 1, time_pair=True)

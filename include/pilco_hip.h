@@ -275,7 +275,9 @@ int pilco_rollout_grad_rbf_group(pilco_ctx** ctxs, int n, const pilco_policy* po
  *   handles by any host transport, pilco_peer_attach(handles[nranks][64]).  share_gpu != 0 when ranks share a GPU
  *   (oversubscribed tests): the flag wait then runs as a one-workgroup launch of its own so that waiting kernels cannot
  *   keep the awaited ones off the machine.
- *   contexts of one process: pilco_group_peer_attach(ctxs, n).
+ *   contexts of one process: pilco_group_peer_attach(ctxs, n).  When they share a GPU, pilco_rollout_group enqueues the
+ *   ranks' launches step by step in lockstep and without a graph: their streams may share hardware queues, and every
+ *   push of a step is then in the queues before any wait for it.
  * A wait that gives up (~2 s) makes pilco_rollout return PILCO_E_STATE instead of hanging.  All ranks must make the same
  * sequence of pilco_rollout calls.  pilco_shard_set / pilco_comm_init detach. */
 #define PILCO_PEER_HANDLE_BYTES 64

@@ -423,6 +423,11 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
             }
         }
         const int spin = 2000000;   // ~2 s of polling before a wait gives up
+        // Contexts of ONE process sharing a GPU (pilco_rollout_group after pilco_group_peer_attach): their streams may share
+        // hardware queues, which start their packets in order, so a rank's flag wait could sit in a queue ahead of the push
+        // it waits for.  The ranks' host threads therefore enqueue in lockstep -- every rank's push of step h is in the
+        // queues before any rank's wait for it -- and run_rollout does not capture these rollouts into a graph.
+        PeerGroup* lockstep = (x.wait_kernel && ctx->group) ? ctx->group.get() : nullptr;
         auto with_xq = [&](GlueArgs& ga, int k) {
             ga.xq = x.local;
             ga.xq_k = k;
@@ -468,6 +473,7 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
             with_xq(gp, h);
             gp.xq_peers = x.d_peers;
             launch_glue(ctx->st, gp);
+            if (lockstep && !lockstep->arrive_and_wait()) return fail(ctx, PILCO_E_STATE, "rollout: another rank of the group failed");
         }
         GlueArgs gf = g;
         gf.step = H;
@@ -612,7 +618,8 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
         ctx->timed_pairs = (s.wk.PL > 0) ? H : 0;
         return PILCO_OK;
     }
-    if (!ctx->use_graph || (sharded && (!ctx->comm || ctx->graph_rccl_failed)) || (ctx->dbg && !getenv("PILCO_DBG_GRAPH")))
+    const bool lockstep = peer && ctx->group && ctx->xq.wait_kernel;   // enqueued step by step with the group (enqueue_rollout_steps)
+    if (!ctx->use_graph || lockstep || (sharded && (!ctx->comm || ctx->graph_rccl_failed)) || (ctx->dbg && !getenv("PILCO_DBG_GRAPH")))
         return enqueue_rollout(ctx, plan, H, nullptr);
     const GlueArgs& g = plan.g;
     std::vector<unsigned long long> key = {

@@ -95,11 +95,8 @@ def test_one_learning_iteration_ends_where_the_executed_reference_ends(standin, 
     stand-in) must end with the same hyper-parameters, the same controller and the same predicted reward: constructor
     draws, restart draws and their order, which fit / controller is kept, transforms, priors, optimiser options all match."""
     from oracle import ref_exec
-    if not ref_exec.available():
-        pytest.skip("/root/reference is not present on this box")
+    from helpers.stored_reference import executed_or_stored
     from pilco_amd.models import PILCO
-    R = ref_exec.load()
-    n_ = ref_exec.to_np
     rs = np.random.RandomState(3)
     X = rs.randn(40, 3)
     f = lambda Z: np.stack([0.3 * np.sin(Z[:, 0]) + 0.2 * Z[:, 2], 0.25 * np.cos(Z[:, 1]) * Z[:, 0]], 1)
@@ -133,8 +130,12 @@ def test_one_learning_iteration_ends_where_the_executed_reference_ends(standin, 
 
     import contextlib
     import io
+    def executed():
+        R = ref_exec.load()
+        return script(R.PILCO, R.controllers.RbfController, ref_exec.to_np)
+
     with contextlib.redirect_stdout(io.StringIO()):
-        ref = script(R.PILCO, R.controllers.RbfController, n_)
+        ref = executed_or_stored("learning_iteration_" + policy, executed)
         from pilco_amd.controllers import RbfController
         ours = script(PILCO, RbfController, lambda v: np.asarray(v.numpy() if hasattr(v, "numpy") else v))
     assert ours["tail"] == ref["tail"]                      # the same number of draws consumed from NumPy's global generator
@@ -150,12 +151,9 @@ def test_one_safe_pilco_iteration_ends_where_the_executed_extension_ends(standin
     import contextlib
     import io
     from oracle import ref_exec
-    if not ref_exec.available():
-        pytest.skip("/root/reference is not present on this box")
+    from helpers.stored_reference import executed_or_stored
     from pilco_amd.rewards import ExponentialReward
     from pilco_amd.safe import SafePILCO, SingleConstraint
-    Rs = ref_exec.load(safe=True)
-    n_ = ref_exec.to_np
     rs = np.random.RandomState(4)
     X = rs.randn(36, 3)
     Y = np.stack([0.3 * np.sin(X[:, 0]) + 0.2 * X[:, 2], 0.25 * np.cos(X[:, 1]) * X[:, 0]], 1) + 0.02 * rs.randn(36, 2)
@@ -170,10 +168,14 @@ def test_one_safe_pilco_iteration_ends_where_the_executed_extension_ends(standin
         return dict(W=to_np(p.controller.W), b=to_np(p.controller.b), r0=r0, r=float(np.ravel(to_np(p.compute_reward()))[0]),
                     tail=np.random.normal())
 
+    def executed():
+        Rs = ref_exec.load(safe=True)
+        return script(lambda: Rs.safe_pilco.SafePILCO((X, Y), horizon=4, reward_add=Rs.rewards.ExponentialReward(2),
+                                                      reward_mult=Rs.rewards_safe.SingleConstraint(0, high=0.8, inside=False),
+                                                      mu=-2.0, m_init=m0, S_init=S0), ref_exec.to_np)
+
     with contextlib.redirect_stdout(io.StringIO()):
-        ref = script(lambda: Rs.safe_pilco.SafePILCO((X, Y), horizon=4, reward_add=Rs.rewards.ExponentialReward(2),
-                                                     reward_mult=Rs.rewards_safe.SingleConstraint(0, high=0.8, inside=False),
-                                                     mu=-2.0, m_init=m0, S_init=S0), n_)
+        ref = executed_or_stored("safe_pilco_iteration", executed)
         ours = script(lambda: SafePILCO((X, Y), horizon=4, reward_add=ExponentialReward(2),
                                         reward_mult=SingleConstraint(0, high=0.8, inside=False), mu=-2.0, m_init=m0, S_init=S0),
                       lambda v: np.asarray(v.numpy() if hasattr(v, "numpy") else v))

@@ -948,9 +948,10 @@ def test_sharded_rollout_group_of_contexts(E, U, nranks, sparse):
             assert mm2 == 0 and np.array_equal(M2, M) and np.array_equal(S2, S) and np.array_equal(R2, R)
             if nranks > 1:
                 # the same rollout with the PEER EXCHANGE: every rank stores its segment straight into the other ranks'
-                # exchange areas and raises a flag, the next head waits on the flags -- no host barrier, no collective,
-                # the whole sharded rollout one hipGraph per rank.  Bit-identical to the host-mediated run; repeated
-                # (graph replay), with another horizon (epochs carry over between rollouts) and eagerly.
+                # exchange areas and raises a flag, the next head waits on the flags -- no collective, no host copy (the
+                # contexts of this process enqueue in lockstep: their streams may share hardware queues).  Bit-identical
+                # to the host-mediated run; repeated, with another horizon (epochs carry over between rollouts) and with
+                # the graph switched off.
                 _lib.group_peer_attach(group)
                 assert all(cx.peer_attached() for cx in group)
                 for rep in range(3):
@@ -2000,13 +2001,14 @@ def test_policy_gradient_wide_inputs_vs_autograd(ctx, dims):
     np.testing.assert_allclose(bb, bt.grad.numpy(), rtol=1e-6, atol=1e-9 * np.abs(bt.grad.numpy()).max())
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 3, 4])
 def test_bench_ranks_in_separate_processes_peer_exchange_on_one_gpu(world):
     """bench.py --gpus N exactly as the driver launches it (torch.distributed.run, one PROCESS per rank), all ranks on
     this box's single GPU (PILCO_BENCH_SHARE_GPU=1: RCCL refuses duplicate devices, so the beta rows travel over gloo): the
     sharded factorisation, the hipIpc-mapped exchange areas, the flag waits between processes and the graph replay of the
     sharded rollout; bench.py itself verifies the rollout against the executed-reference fixture and reports the exchange
-    it used.  world = 8 is BASELINE config 3's rank count: eight processes, eight exchange areas mapped into each other, one GPU."""
+    it used.  world <= 4: with this process and the launcher that is six processes on the GPU, the most a shared machine
+    takes at once; BASELINE config 3's eight ranks run as contexts of one process in test_sharded_rollout_group_of_contexts."""
     import json
     import socket
     import subprocess

@@ -148,25 +148,33 @@ def test_constraints_inside_a_combined_reward_as_the_reference_safe_swimmer_scri
     import io
     import torch
     from oracle import ref_exec
-    import pytest
-    if not ref_exec.available():
-        pytest.skip("/root/reference is not present on this box")
+    from helpers.stored_reference import executed_or_stored
     from pilco_amd.safe import SingleConstraint
     from pilco_amd.training import _policy_params, policy_loss_and_grad
-    Rs = ref_exec.load(safe=True)
-    n_ = ref_exec.to_np
     g = np.load(os.path.join(GOLDEN, "policy_optimisation.npz"))
     E, H = 2, 5
     Wl = np.array([[0.4], [-0.3]])
-    ref = Rs.PILCO((g["X"], g["Y"]), horizon=H, m_init=g["m"], S_init=g["s"],
-                   reward=Rs.rewards.CombinedRewards(E, [Rs.rewards.LinearReward(E, Wl), Rs.rewards.ExponentialReward(E),
-                                                          Rs.rewards_safe.SingleConstraint(0, low=-0.5, high=0.9, inside=False),
-                                                          Rs.rewards_safe.SingleConstraint(1, high=0.4)], coefs=[1.0, 0.5, -3.0, 0.7]))
-    for i, mdl in enumerate(ref.mgpr.models):
-        mdl.kernel.lengthscales.assign(g["lengthscales"][i]); mdl.kernel.variance.assign(g["variance"][i]); mdl.likelihood.variance.assign(g["noise"][i])
-    ref.controller.W.assign(g["W"]); ref.controller.b.assign(g["b"]); ref.controller.max_action = g["max_action"]
-    loss = ref.training_loss()
-    gW, gb = torch.autograd.grad(loss.sum(), [ref.controller.W.unconstrained_variable, ref.controller.b.unconstrained_variable])
+
+    def executed():
+        Rs = ref_exec.load(safe=True)
+        n_ = ref_exec.to_np
+        ref = Rs.PILCO((g["X"], g["Y"]), horizon=H, m_init=g["m"], S_init=g["s"],
+                       reward=Rs.rewards.CombinedRewards(E, [Rs.rewards.LinearReward(E, Wl), Rs.rewards.ExponentialReward(E),
+                                                              Rs.rewards_safe.SingleConstraint(0, low=-0.5, high=0.9, inside=False),
+                                                              Rs.rewards_safe.SingleConstraint(1, high=0.4)], coefs=[1.0, 0.5, -3.0, 0.7]))
+        for i, mdl in enumerate(ref.mgpr.models):
+            mdl.kernel.lengthscales.assign(g["lengthscales"][i]); mdl.kernel.variance.assign(g["variance"][i]); mdl.likelihood.variance.assign(g["noise"][i])
+        ref.controller.W.assign(g["W"]); ref.controller.b.assign(g["b"]); ref.controller.max_action = g["max_action"]
+        loss = ref.training_loss()
+        gW, gb = torch.autograd.grad(loss.sum(), [ref.controller.W.unconstrained_variable, ref.controller.b.unconstrained_variable])
+        mu_r, var_r = ref.reward.compute_reward(g["m"], g["s"])            # CombinedRewards.compute_reward itself (rewards.py:73-81)
+        out = dict(loss=float(n_(loss).ravel()[0]), gW=gW.numpy(), gb=gb.numpy(), mu=np.ravel(n_(mu_r)), var=np.ravel(n_(var_r)))
+        with contextlib.redirect_stdout(io.StringIO()):
+            ref.optimize_policy(maxiter=6, restarts=1)
+        out.update(reward_opt=float(n_(ref.compute_reward()).ravel()[0]), W_opt=n_(ref.controller.W))
+        return out
+
+    ref = executed_or_stored("combined_reward_constraints", executed)
 
     from helpers.cpu_standin_context import CpuStandInContext
     ctx = CpuStandInContext()
@@ -178,21 +186,18 @@ def test_constraints_inside_a_combined_reward_as_the_reference_safe_swimmer_scri
     _hyp(p, g)
     ctl.W.assign(g["W"]); ctl.b.assign(g["b"])
     assert len(rew.terms()) == 2 and len(rew.host_terms()) == 2
-    np.testing.assert_allclose(float(p.compute_reward()[0, 0]), -float(n_(loss).ravel()[0]), rtol=1e-9)
+    np.testing.assert_allclose(float(p.compute_reward()[0, 0]), -ref["loss"], rtol=1e-9)
     get, put = _policy_params(ctl)
     f, grad = policy_loss_and_grad(p, get(), put)
-    np.testing.assert_allclose(f, float(n_(loss).ravel()[0]), rtol=1e-9)
-    np.testing.assert_allclose(grad[:2].reshape(1, 2), gW.numpy(), rtol=1e-7)
-    np.testing.assert_allclose(grad[2:].reshape(1, 1), gb.numpy(), rtol=1e-7)
-    mu_r, var_r = ref.reward.compute_reward(g["m"], g["s"])            # CombinedRewards.compute_reward itself (rewards.py:73-81)
+    np.testing.assert_allclose(f, ref["loss"], rtol=1e-9)
+    np.testing.assert_allclose(grad[:2].reshape(1, 2), ref["gW"], rtol=1e-7)
+    np.testing.assert_allclose(grad[2:].reshape(1, 1), ref["gb"], rtol=1e-7)
     mu_o, var_o = rew.compute_reward(g["m"], g["s"])
-    np.testing.assert_allclose(np.ravel(mu_o), np.ravel(n_(mu_r)), rtol=1e-9)
-    np.testing.assert_allclose(np.ravel(var_o), np.ravel(n_(var_r)), rtol=1e-7)
-    with contextlib.redirect_stdout(io.StringIO()):
-        ref.optimize_policy(maxiter=6, restarts=1)
+    np.testing.assert_allclose(np.ravel(mu_o), ref["mu"], rtol=1e-9)
+    np.testing.assert_allclose(np.ravel(var_o), ref["var"], rtol=1e-7)
     r = p.optimize_policy(maxiter=6, restarts=1, verbose=False)
-    np.testing.assert_allclose(r, float(n_(ref.compute_reward()).ravel()[0]), rtol=1e-6)
-    np.testing.assert_allclose(ctl.W.numpy(), n_(ref.controller.W), rtol=1e-3, atol=1e-6)
+    np.testing.assert_allclose(r, ref["reward_opt"], rtol=1e-6)
+    np.testing.assert_allclose(ctl.W.numpy(), ref["W_opt"], rtol=1e-3, atol=1e-6)
 
 
 def test_objective_function_reward_takes_the_analytic_path():
