@@ -99,6 +99,16 @@ int pilco_gp_set_factors(pilco_ctx* ctx, int slot, const double* iK, const doubl
  * pilco_gp_predict = predict_on_noisy_inputs (mgpr.py:77-79) with the
  * factorisation cached instead of recomputed. */
 int pilco_gp_predict(pilco_ctx* ctx, int slot, const double* m, const double* s, double* M, double* S, double* V);
+/* GPflow GPR.predict_f / GPRFITC.predict_f (full_cov=False) of the model in `slot` at Nt deterministic inputs
+ * Xs (Nt, D): latent mean (E, Nt) and latent variance (E, Nt), output-major.  output = -1: all E outputs;
+ * 0 <= output < E: that output only (mean, var hold Nt values).  Z_all (sparse slots only, may be NULL):
+ * (E, M, D), output e's own inducing inputs; NULL = the slot's Z for every output.
+ * Needs the slot's own factorisation (factorises if it is not current; PILCO_E_STATE after pilco_gp_set_factors or on a
+ * sharded context) and leaves it unchanged.  Every test point's result is computed in a fixed order that does not depend
+ * on the other points of the call: a point gives the same bits alone or in any batch.  Chunked over the test points:
+ * bounded memory for any Nt. */
+int pilco_gp_predict_points(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int output, const double* Z_all,
+                            double* mean, double* var);
 
 /* ------------------------------------------------------------------ rollout */
 typedef enum pilco_policy_kind {

@@ -75,6 +75,7 @@ SIGNATURES = {
     "pilco_gp_get_factors": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "pilco_gp_set_factors": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "pilco_gp_predict": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_gp_predict_points": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "pilco_rollout": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                 _dp, _dp, _dp, _dp]),
     "pilco_gp_predict_vjp": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -328,6 +329,23 @@ class Context:
         V = np.empty((D, E))
         self._chk(self.lib.pilco_gp_predict(self.h, slot, _ptr(m), _ptr(s), _ptr(M), _ptr(S), _ptr(V)))
         return M, S, V
+
+    def gp_predict_points(self, slot, Xs, D, E, output=-1, Z_all=None):
+        """GPR / GPRFITC predict_f at deterministic inputs Xs (Nt, D): latent mean and variance, (E, Nt) each, or (1, Nt)
+        for one output (0 <= output < E).  Z_all (E, M, D): every output's own inducing inputs (sparse slots only)."""
+        Xs = _f64(Xs)
+        if Xs.ndim != 2 or Xs.shape[1] != D:
+            raise ValueError(f"test inputs must be (Nt, {D})")
+        Nt = Xs.shape[0]
+        Za = None
+        if Z_all is not None:
+            Za = _f64(Z_all)
+            Za = _f64(Za, (E, Za.shape[-2], D))
+        rows = E if output < 0 else 1
+        mean = np.empty((rows, Nt))
+        var = np.empty((rows, Nt))
+        self._chk(self.lib.pilco_gp_predict_points(self.h, slot, _ptr(Xs), Nt, int(output), _ptr(Za), _ptr(mean), _ptr(var)))
+        return mean, var
 
     # ---- policy / reward marshalling
     def _policy(self, spec):

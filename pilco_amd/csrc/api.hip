@@ -366,6 +366,7 @@ int pilco_ctx_destroy(pilco_ctx* ctx) {
         for (ChainGraph* cg : {&sl.g_fact, &sl.g_fitc, &sl.g_fitc_nlml}) chain_graph_release(*cg);
     if (ctx->comm) ncclCommDestroy(ctx->comm);
     for (Slot& s : ctx->slot) {
+        predict_release(s);
         for (DevBuf* b : {&s.Xt, &s.Yt, &s.Zt, &s.ls, &s.var, &s.noise, &s.K, &s.Linv, &s.iK, &s.beta, &s.Tscr, &s.ksplit_ws,
                           &s.vec, &s.Kmn, &s.V2, &s.bwd_mom, &s.bwd_cp, &s.bwd_part, &s.bwd_out, &s.bwd_cnt, &s.jac_rowmom, &s.jac_cpart, &s.jac_head, &s.jac_part, &s.jac_np, &s.own, &s.Am, &s.AmInv, &s.iAt, &s.G, &s.w_in, &s.w_At, &s.w_Wt, &s.w_small, &s.w_fpart,
                           &s.w_part, &s.w_gath, &s.w_out, &s.ft_P, &s.ft_T3, &s.ft_Z})
@@ -955,12 +956,13 @@ int pilco_factorize_fitc(pilco_ctx* ctx, void* slot_ptr) {
     for (const void* q : {(const void*)o.ls, (const void*)o.var, (const void*)o.noise, (const void*)o.Yt, (const void*)ctx->d_info})
         key.push_back((unsigned long long)(uintptr_t)q);
     for (int v : {Mp, Np, s.M, s.N, s.D, EL, o.W, o.rank, o.ELcap}) key.push_back((unsigned long long)v);
+    key.push_back((unsigned long long)s.Zstride);
     auto chain = [&]() -> int {
     HIPCHK(hipMemsetAsync(ctx->d_info, 0, sizeof(int) * 64, st));
     if (o.W > 1) HIPCHK(hipMemsetAsync(s.beta.p, 0, sizeof(double) * (size_t)o.W * o.ELcap * Mp, st));
     // smgpr.py:27-28: Kmm = K(Z) + 1e-6 I, Kmn = K(Z, X)
-    launch_gram(st, s.Zt.p, Mp, s.M, s.Zt.p, Mp, s.M, s.D, o.ls, o.var, E, s.K.p, Mp, Mp, 2, nullptr, 1e-6);
-    launch_gram(st, s.Zt.p, Mp, s.M, s.Xt.p, Np, s.N, s.D, o.ls, o.var, E, s.Kmn.p, Mp, Np, 0, nullptr, 0.0);
+    launch_gram(st, s.Zt.p, Mp, s.M, s.Zt.p, Mp, s.M, s.D, o.ls, o.var, E, s.K.p, Mp, Mp, 2, nullptr, 1e-6, s.Zstride, s.Zstride);
+    launch_gram(st, s.Zt.p, Mp, s.M, s.Xt.p, Np, s.N, s.D, o.ls, o.var, E, s.Kmn.p, Mp, Np, 0, nullptr, 0.0, s.Zstride, 0);
     launch_potrf(st, s.K.p, Mp, E, s.Linv.p, ctx->d_info, true);                // smgpr.py:29
     launch_trtri(st, s.K.p, Mp, E, s.Linv.p, s.Tscr.p, (long)Mp * Mp);
     GemmDesc g{};

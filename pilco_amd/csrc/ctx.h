@@ -24,6 +24,8 @@ struct ChainGraph {
     bool failed = false;
 };
 
+struct PredictWork;   // predict.hip
+
 struct Slot {
     ChainGraph g_fact, g_fitc, g_fitc_nlml;   // exact / FITC factorisation, the FITC training objective (the exact objective = the factorisation's graph + two eager launches)
     int N = 0, D = 0, E = 0, M = 0;  // data size, input dim, outputs, inducing points (0 = exact)
@@ -38,6 +40,8 @@ struct Slot {
     DevBuf ksplit_ws;                          // partial products of the split-K GEMMs of the FITC path (GemmDesc::split_ws)
     DevBuf Kmn, V2, Am, AmInv, iAt, G;         // FITC extras
     DevBuf ft_P, ft_T3, ft_Z;                  // FITC training objective (fitc_train.hip)
+    long Zstride = 0;                          // doubles between the outputs' inducing sets in Zt (0: one set shared by every output)
+    PredictWork* pred = nullptr;               // pilco_gp_predict_points: its buffers, and the FITC operands of per-output inducing inputs
     // sharded factorisation (8e): this rank factorises only its outputs a = rank, rank + shW, ...; `own` holds their
     // hyper-parameters and targets compacted ([EL][D] | [EL] | [EL] | [EL][Npad]); beta is all-gathered afterwards
     DevBuf own;
@@ -230,6 +234,8 @@ int build_work(pilco_ctx* ctx, Slot& s);          // (re)builds the per-slot ste
 MMModel model_of(const Slot& s);
 int all_gather_segments(pilco_ctx* ctx, Slot& s);
 int pilco_factorize_fitc(pilco_ctx* ctx, void* slot_ptr);
+// predict.hip
+void predict_release(Slot& s);   // frees Slot::pred
 
 // rollout.hip
 struct RolloutPlan {

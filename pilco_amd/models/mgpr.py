@@ -120,6 +120,29 @@ class MGPR:
         self._ensure_factorized()
         return self.ctx.gp_predict(self._slot, m, s, self.num_dims, self.num_outputs)
 
+    # -- gpflow GPR.predict_f / predict_y of the output models (mgpr.py:28-36 builds them), all outputs in one device call
+    def _own_inducing(self):
+        return None
+
+    def _predict_points(self, Xnew, output=-1):
+        """(mean, var) of the latent functions at Xnew (Nt, D): (Nt, E) each, or (Nt, 1) for one output."""
+        self._user_factors = None
+        self._ensure_factorized()
+        mean, var = self.ctx.gp_predict_points(self._slot, np.asarray(Xnew, np.float64).reshape(-1, self.num_dims), self.num_dims,
+                                               self.num_outputs, output, self._own_inducing())
+        return tensor_value(mean.T), tensor_value(var.T)
+
+    def predict_f(self, Xnew, full_cov=False):
+        """Every output's GPR.predict_f at Xnew (Nt, D): mean and latent variance, (Nt, E) each (extension)."""
+        if full_cov:
+            raise NotImplementedError("predict_f: only full_cov=False (the marginal variances) is supported")
+        return self._predict_points(Xnew)
+
+    def predict_y(self, Xnew):
+        """predict_f with every output's likelihood variance added to its variance (extension)."""
+        mean, var = self._predict_points(Xnew)
+        return mean, tensor_value(np.asarray(var) + self.noise.reshape(1, -1))
+
     # -- reference: mgpr.py:81-89
     def calculate_factorizations(self):
         self._user_factors = None

@@ -49,6 +49,10 @@ class SMGPR(MGPR):
     def _points(self):
         return self.Z
 
+    def _own_inducing(self):
+        """predict_f of output i uses output i's own inducing inputs (its GPRFITC model), not model 0's."""
+        return np.stack([np.asarray(m.inducing_variable.Z.numpy(), np.float64) for m in self.models])
+
     # -- reference: MGPR.optimize applied to GPRFITC models (mgpr.py:47-75 with smgpr.py:16-22)
     def optimize(self, restarts=1, keep="last"):
         """Every output's GPRFITC model is fitted as the reference does it: kernel hyper-parameters, noise variance AND

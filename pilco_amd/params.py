@@ -116,3 +116,15 @@ class GPModelView:
     def data(self):
         X, Y = self._owner._X, self._owner._Y
         return (X, Y[:, self.index:self.index + 1])
+
+    def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
+        """gpflow GPR.predict_f / GPRFITC.predict_f of this output at Xnew (Nt, D): latent mean and variance, (Nt, 1) each,
+        computed on the device (pilco_gp_predict_points)."""
+        if full_cov or full_output_cov:
+            raise NotImplementedError("predict_f: only full_cov=False, full_output_cov=False (the marginal variances) is supported")
+        return self._owner._predict_points(Xnew, self.index)
+
+    def predict_y(self, Xnew, full_cov=False, full_output_cov=False):
+        """gpflow's Gaussian-likelihood predict_y: predict_f with the likelihood variance added to the variance."""
+        mean, var = self.predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
+        return mean, tensor_value(np.asarray(var) + float(self.likelihood.variance.numpy()))
