@@ -427,7 +427,12 @@ static int fitc_nlml_batch(pilco_ctx* ctx, Slot& s, int E, const double* o_ls, c
     ENSURE(s.ft_P, E * mn);
     ENSURE(s.ft_T3, E * mn);
     ENSURE(s.ft_Z, (size_t)E * D * Mp + (size_t)E * M * D);
-    ENSURE(s.vec, (size_t)E * (4 * (size_t)std::max(Mp, Np) + 8) + 8 + (size_t)E * ((size_t)D + 3 + (size_t)M * D));
+    // s.vec carve-out (offsets in doubles): r0 [E][Mp] | gam [E][Mp] | av [E][Np] | gv [E][Np] | cv [E][Mp] | sums [4 E + 4] | res [E][RS];
+    // the buffer is sized by the end of this layout
+    const size_t RS = (size_t)D + 3 + (size_t)M * D;         // per output: d ls | d var | d sn2 | gam . gam | d Z
+    const size_t o_gam = (size_t)E * Mp, o_av = o_gam + (size_t)E * Mp, o_gv = o_av + (size_t)E * Np, o_cv = o_gv + (size_t)E * Np;
+    const size_t o_sums = o_cv + (size_t)E * Mp, o_res = o_sums + 4 * (size_t)E + 4, vec_end = o_res + (size_t)E * RS;
+    ENSURE(s.vec, vec_end);
     double* Zt = s.ft_Z.p;                       // [E][D][Mp]
     double* Zraw = Zt + (size_t)E * D * Mp;      // [E][M][D] staging
     const long sZ = (long)D * Mp;
@@ -435,13 +440,12 @@ static int fitc_nlml_batch(pilco_ctx* ctx, Slot& s, int E, const double* o_ls, c
     double* V = s.V2.p;
     const bool want_grad = grad_hyp || grad_Z;
     double* r0 = s.vec.p;                                    // [E][Mp]  Vb (y / G)
-    double* gam = r0 + (size_t)E * Mp;                       // [E][Mp]  AmInv r0 = gamma sn   (gamma = L^-1 U ytil)
-    double* av = gam + (size_t)E * Mp;                       // [E][Np]
-    double* gv = av + (size_t)E * Np;                        // [E][Np]
-    double* cv = gv + (size_t)E * Np;                        // [E][Mp]
-    double* sums = cv + (size_t)E * Mp;                      // [E][3] + logdet [E]
-    const size_t RS = (size_t)D + 3 + (size_t)M * D;         // per output: d ls | d var | d sn2 | gam . gam | d Z
-    double* res = sums + 4 * (size_t)E + 4;                  // [E][RS]
+    double* gam = s.vec.p + o_gam;                           // [E][Mp]  AmInv r0 = gamma sn   (gamma = L^-1 U ytil)
+    double* av = s.vec.p + o_av;                             // [E][Np]
+    double* gv = s.vec.p + o_gv;                             // [E][Np]
+    double* cv = s.vec.p + o_cv;                             // [E][Mp]
+    double* sums = s.vec.p + o_sums;                         // [E][3] + logdet [E]
+    double* res = s.vec.p + o_res;                           // [E][RS]
     // per-row partial sums of the two kernel-derivative reductions: Kuf's in nsp slices of the points, then Kuu's
     const bool kg_mfma = D <= 14 && getenv("PILCO_FITC_KGRAD_VALU") == nullptr;
     const int nsp = kg_mfma ? (N >= 2048 ? FT_NSPLIT : 1) : 1;

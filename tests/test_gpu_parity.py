@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from helpers.fitc_objective import fitc_loss_np as _fitc_loss_np, fitc_reference
 from oracle import tf_path as tp
 from pilco_amd import synthetic
 
@@ -1504,6 +1505,12 @@ def test_fitc_training_objective_and_gradients(ctx, golden_dir):
     nl, gh2, gz2 = ctx.gp_fitc_nlml(0, Zb, 4, 3)
     for e in range(3):
         np.testing.assert_allclose(nl[e], _fitc_loss_np(c["X"], c["Y"][:, e], Zb[e], c["lengthscales"][e], c["variance"][e], c["noise"][e]), rtol=1e-9)
+    # ... and every gradient (lengthscales, variance, noise, Z) vs torch autograd of the restatement
+    rn, rh, rz = fitc_reference(c["X"], c["Y"], Zb, c["lengthscales"], c["variance"], c["noise"])
+    for e in range(3):
+        floor = 1e-8 * max(np.abs(rh[e]).max(), np.abs(rz[e]).max())
+        np.testing.assert_allclose(gh2[e], rh[e], rtol=1e-6, atol=floor)
+        np.testing.assert_allclose(gz2[e], rz[e], rtol=1e-6, atol=floor)
     u = np.log(c["lengthscales"])
     for (e, d) in [(0, 1), (2, 3)]:
         lp, lm = c["lengthscales"].copy(), c["lengthscales"].copy()
@@ -1512,22 +1519,6 @@ def test_fitc_training_objective_and_gradients(ctx, golden_dir):
         fp = _fitc_loss_np(c["X"], c["Y"][:, e], Zb[e], lp[e], c["variance"][e], c["noise"][e])
         fm = _fitc_loss_np(c["X"], c["Y"][:, e], Zb[e], lm[e], c["variance"][e], c["noise"][e])
         np.testing.assert_allclose(gh2[e, d], (fp - fm) / (2e-6 * c["lengthscales"][e, d]), rtol=1e-4)
-
-
-def _fitc_loss_np(X, y, Z, ls, var, noise, jitter=1e-6):
-    """NumPy restatement of gpflow GPRFITC's negative log marginal likelihood (one output)."""
-    import scipy.linalg as sla
-    N, M = X.shape[0], Z.shape[0]
-    Kuf = tp.se_ard_K(Z, X, ls[None, :], np.array([var]))[0]
-    Kuu = tp.se_ard_K(Z, None, ls[None, :], np.array([var]))[0] + jitter * np.eye(M)
-    Luu = np.linalg.cholesky(Kuu)
-    V = sla.solve_triangular(Luu, Kuf, lower=True)
-    nu = var - np.sum(V * V, 0) + noise
-    B = np.eye(M) + (V / nu) @ V.T
-    L = np.linalg.cholesky(B)
-    gamma = sla.solve_triangular(L, V @ (y / nu), lower=True)
-    f = -0.5 * np.sum(y * y / nu) + 0.5 * gamma @ gamma - 0.5 * N * np.log(2 * np.pi) - 0.5 * np.sum(np.log(nu)) - np.sum(np.log(np.diag(L)))
-    return -f
 
 
 def test_sparse_optimize_models_runs_and_predicts(ctx, monkeypatch):
