@@ -331,7 +331,7 @@ int pilco_ctx_create(int device, pilco_ctx** out) {
     {
         const int tn = mm_exp_table_size();
         std::vector<double> tab(tn);
-        for (int j = 0; j < tn; ++j) tab[j] = std::exp2((double)j / (double)tn);
+        mm_exp_table_fill(tab.data());
         if (ctx->exp_tab.ensure(tn) != hipSuccess ||
             hipMemcpy(ctx->exp_tab.p, tab.data(), sizeof(double) * tn, hipMemcpyHostToDevice) != hipSuccess) {
             delete ctx;

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
         if (h < md.E + wk.PL) bwd_head(md, wk, bars, h, head, csl);
         return;
     }
-    for (int e = threadIdx.x; e < FEXP_TN; e += blockDim.x) tab[e] = wk.exp_tab[e];
+    for (int e = threadIdx.x; e < FEXP_TN; e += blockDim.x) tab[e] = fexp_table_unbias(wk.exp_tab[e], e);   // (fexp_ub: mm_device.h)
     const int npad = md.npad, D = md.D, E = md.E;
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (the wave index in scalar registers: the diagonal pairs' tile tests are scalar)
     const int lr = lane >> 4, lc = lane & 15;
@@ -324,13 +324,13 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
                             // the column side beta_a,i only (one multiply and one FMA instead of two multiplies and an
                             // add); the epilogue / k_mm_bwd_post apply the missing factor per row / per column
                             // (beta_b,j rides in the moment product's column operand a2, scaled once per column step)
-                            const double l = fexp_to_mfma(e[r], tab);   // (straight into the moment product's A operand: mm_device.h)
+                            const double l = fexp_ub_to_mfma(e[r], tab);   // (straight into the moment product's A operand: mm_device.h)
                             wl[r] = l;
                             csum[r] = fma(brow[rt], l, csum[r]);
                         } else {
                             double wgt = brow[rt] * bcol[r];
                             if (MODE == 1) wgt -= ikn[rt][r];   // iK symmetric: coalesced along the rows (requested a step ago)
-                            wl[r] = (wgt * om) * fexp(e[r], tab);
+                            wl[r] = (wgt * om) * fexp_ub(e[r], tab);
                             csum[r] += wl[r];
                         }
                     }

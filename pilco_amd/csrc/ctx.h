@@ -133,7 +133,7 @@ struct pilco_ctx {
     hipEvent_t jwait_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // behind the chunks of the records' download (last steps first)
     int jwait_t0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, jwait_n = 0, jwait_next = 0, jwait_from = 0;   // first step of chunk k; steps >= jwait_from are on the host
     DevBuf selftest;
-    DevBuf exp_tab;  // 2^(j/n), j = 0..n-1, n = mm_exp_table_size()
+    DevBuf exp_tab;  // 2^(j/n), j = 0..n-1, n = mm_exp_table_size(), high words biased (mm_exp_table_fill)
     unsigned long long* dbg = nullptr;   // [PILCO_DBG_WORDS] developer stamps (pilco_debug_timestamps allocates it)
     // cached hipGraph of one rollout (single-rank): replayed while the plan key is unchanged
     hipGraphExec_t graph = nullptr;

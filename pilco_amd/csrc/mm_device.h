@@ -194,7 +194,33 @@ __device__ __forceinline__ double fexp_poly(double x, double t) {
     q = fma(r, q, 1.0);
     return r * q;
 }
-__device__ __forceinline__ double fexp_finish(double tv, double pm1, double t) {
+// The exponent goes into the TABLE VALUE before the final FMA, not into the result after it: the host stores entry j with
+// its high word lowered by j << (20 - FEXP_TB) (mm_exp_table_fill), so ONE integer add of lo(t) << (20 - FEXP_TB) = n << 12
+// (n = T m + j, exact mod 2^32 for negative n too) turns it into 2^m tab[j] -- no mask of the index bits: one VALU op
+// fewer per exp than fexp_finish_ub, same bits (tests/test_fexp_table_cpu.py).  fma(2^m tv, p, 2^m tv) = 2^m fma(tv, p, tv)
+// bit for bit while everything is normal, which the -700 clamp ensures.  Written in C: the compiler's own v_lshl_add_u32.
+__device__ __forceinline__ double fexp_scale(double tvb, double t) {
+    const int hi = __double2hiint(tvb) + (__double2loint(t) << (20 - FEXP_TB));
+    return __hiloint2double(hi, __double2loint(tvb));
+}
+__device__ __forceinline__ double fexp_finish(double tvb, double pm1, double t) {
+    const double tv = fexp_scale(tvb, t);
+    return fma(tv, pm1, tv);
+}
+__device__ __forceinline__ double fexp(double x, const double* __restrict__ tab) {
+    x = fexp_clamp(x);
+    const double t = fexp_t(x);
+    const double tv = tab[__double2loint(t) & (FEXP_TN - 1)];
+    return fexp_finish(tv, fexp_poly(x, t), t);
+}
+// The same exp over an UNBIASED table (2^(j/T) as it is: fexp_table_unbias when the table is copied to LDS), the exponent
+// inserted into the result after the FMA -- one v_and more per exp.  Kept by the reverse sweep and the fused small step:
+// there the biased form measured slower (the sweep's K = 3 instantiations spill more registers; config 4 -3 %), see
+// docs/dead_ends.md.  Both forms give the same bits.
+__device__ __forceinline__ double fexp_table_unbias(double tvb, int j) {
+    return __hiloint2double(__double2hiint(tvb) + (j << (20 - FEXP_TB)), __double2loint(tvb));
+}
+__device__ __forceinline__ double fexp_finish_ub(double tv, double pm1, double t) {
     const double res = fma(tv, pm1, tv);
     const int lo = __double2loint(t) & ~(FEXP_TN - 1);
     int hi;
@@ -205,21 +231,21 @@ __device__ __forceinline__ double fexp_finish(double tv, double pm1, double t) {
 #endif
     return __hiloint2double(hi, __double2loint(res));
 }
-__device__ __forceinline__ double fexp(double x, const double* __restrict__ tab) {
+__device__ __forceinline__ double fexp_ub(double x, const double* __restrict__ tab) {
     x = fexp_clamp(x);
     const double t = fexp_t(x);
     const double tv = tab[__double2loint(t) & (FEXP_TN - 1)];
-    return fexp_finish(tv, fexp_poly(x, t), t);
+    return fexp_finish_ub(tv, fexp_poly(x, t), t);
 }
-// ... for a result that goes STRAIGHT into an MFMA operand.  gfx950 does not interlock "VALU writes a VGPR -> an MFMA reads
+// ... for a result that goes STRAIGHT into an MFMA operand (unbiased table).  gfx950 does not interlock "VALU writes a VGPR -> an MFMA reads
 // it as SrcA / SrcB": the MFMA must come at least three issue slots behind the write (measured: tools/ubench_srcc_war.hip --
 // next slot and one s_nop 0 read the OLD register, s_nop 1 is enough).  hipcc leaves those wait states behind its own VALU
-// instructions but NOT behind an inline-asm statement: with the exponent insertion written as asm (fexp_finish) the moment
+// instructions but NOT behind an inline-asm statement: with the exponent insertion written as asm the moment
 // product of the reverse sweep's off-diagonal pairs read a weight from before its exponent went in whenever the scheduler put
 // the MFMA within two slots -- round 5's "wrong, run-to-run different sums behind a division" (the division only moved the
 // schedule), and every instantiation's turn sooner or later.  Here the insertion is C: the same single v_lshl_add_u32, an
 // instruction the compiler's hazard recognizer sees.  tools/mfma_hazard_check.py flags the pattern.
-__device__ __forceinline__ double fexp_to_mfma(double x, const double* __restrict__ tab) {
+__device__ __forceinline__ double fexp_ub_to_mfma(double x, const double* __restrict__ tab) {
     x = fexp_clamp(x);
     const double t = fexp_t(x);
     const double tv = tab[__double2loint(t) & (FEXP_TN - 1)];

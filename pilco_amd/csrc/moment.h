@@ -71,7 +71,7 @@ struct MMWork {
     int share_cu;        // the head launches its 128-register build (two workgroups per CU): this context is a lane of a batch call
     int NCS;             // fuse_pair with LDS-resident operands: column splits per (pair, row chunk) -- the launch spreads a small model over
                          // the CUs it would leave idle (grid y = NCH * NCS, NT = NCH * NCS partials per pair); 1 elsewhere
-    const double* exp_tab;    // [n] 2^(j/n), n = mm_exp_table_size(), for the table-driven fp64 exp of the pair kernel
+    const double* exp_tab;    // [n] 2^(j/n) biased (mm_exp_table_fill), n = mm_exp_table_size(), for the table-driven fp64 exp of the pair kernel
     int PL, EL, P, KP, NCH, NCHM, NT, SEG, OUTOFF, rank, nranks;  // NCH / NCHM: row chunks of the pair / mean-part prep workgroups; OUTOFF: offset of the output records inside a segment
 };
 
@@ -257,6 +257,7 @@ RevLocalArgs rev_local_args(int n, const RewardDev* rw, int E, int U, const doub
                             double* loc);
 void launch_rev_chain(hipStream_t st, const RevArgs& a);
 int mm_exp_table_size();   // entries of the 2^(j/n) table the pair kernels were built for
+void mm_exp_table_fill(double* tab);   // [mm_exp_table_size()] its entries, biased for the exp's exponent insertion (mm_device.h)
 int launch_selftest_mfma(hipStream_t st, double* dbuf, double* hbuf, const double* exp_tab);
 
 }  // namespace pilco

@@ -321,14 +321,14 @@ __global__ void k_selftest_mfma(double* out) {
     for (int r = 0; r < 4; ++r) out[lane * 4 + r] = acc[r];
 }
 
-// max relative deviation of the table-driven exp from the library exp over [-720, 8]
+// max relative deviation of the table-driven exp from the library exp over [-720, 700]
 __global__ void k_selftest_fexp(const double* tab_g, double* out) {
     __shared__ double tab[FEXP_TN];
     for (int e = threadIdx.x; e < FEXP_TN; e += blockDim.x) tab[e] = tab_g[e];
     __syncthreads();
     double worst = 0.0;
     for (int i = threadIdx.x; i < 200000; i += blockDim.x) {
-        const double x = -720.0 + 728.0 * ((double)i + 0.37) / 200000.0;
+        const double x = -720.0 + 1420.0 * ((double)i + 0.37) / 200000.0;
         const double ref = exp(fmax(x, -700.0));
         const double got = fexp(x, tab);
         // allowed: 1 ulp of the result + the |x| eps conditioning of the single-constant reduction
@@ -340,6 +340,19 @@ __global__ void k_selftest_fexp(const double* tab_g, double* out) {
 }
 
 int mm_exp_table_size() { return FEXP_TN; }
+
+// entry j: 2^(j/T) with its high word lowered by j << (20 - FEXP_TB), so that fexp_scale's add of n << (20 - FEXP_TB)
+// (n = T m + j) leaves exactly 2^m 2^(j/T) (tests/test_fexp_table_cpu.py)
+void mm_exp_table_fill(double* tab) {
+    for (int j = 0; j < FEXP_TN; ++j) {
+        const double v = std::exp2((double)j / (double)FEXP_TN);
+        uint64_t u;
+        std::memcpy(&u, &v, 8);
+        const uint32_t hi = (uint32_t)(u >> 32) - ((uint32_t)j << (20 - FEXP_TB));
+        u = ((uint64_t)hi << 32) | (u & 0xffffffffull);
+        std::memcpy(&tab[j], &u, 8);
+    }
+}
 
 int launch_selftest_mfma(hipStream_t st, double* dbuf, double* hbuf, const double* exp_tab) {
     hipLaunchKernelGGL(k_selftest_fexp, dim3(1), dim3(256), 0, st, exp_tab, dbuf);

@@ -104,7 +104,9 @@ struct WaveProgress {
         }
     }
 };
-template <int KC, bool DIAG, bool VSEP, bool FENCE = false, bool LDSOP = false>
+// BTAB: the exp table is the biased one (exponent inserted into the table value, fexp_finish: the pair kernels); false: the
+// unbiased copy the fused head keeps in LDS (fexp_finish_ub, see fexp_table_unbias in mm_device.h)
+template <int KC, bool DIAG, bool VSEP, bool FENCE = false, bool LDSOP = false, bool BTAB = true>
 __device__ __forceinline__ double pair_wave(const PairOps& po, const double* __restrict__ At, const double* __restrict__ Bt,
                                             const double* __restrict__ vcol,
                                             const double* __restrict__ beta_a, const double* __restrict__ beta_b,
@@ -241,7 +243,7 @@ __device__ __forceinline__ double pair_wave(const PairOps& po, const double* __r
         for (int i = 0; i < NE; ++i) { tv[i] = x[i]; pm[i] = 0.0; tt[i] = 0.0; }
 #define FEXP_FINISH(a_, b_, c_) (a_)
 #else
-#define FEXP_FINISH(a_, b_, c_) fexp_finish(a_, b_, c_)
+#define FEXP_FINISH(a_, b_, c_) (BTAB ? fexp_finish(a_, b_, c_) : fexp_finish_ub(a_, b_, c_))
 #endif
         if (DIAG) {
             double st[4] = {0.0, 0.0, 0.0, 0.0};

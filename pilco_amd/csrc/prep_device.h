@@ -288,7 +288,7 @@ __device__ __forceinline__ void small_sweep(const MMModel& md, const MMWork& wk,
                 double wl[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const double l = fexp(VSEP ? e[r] + vj[r] : e[r], tab);
+                    const double l = fexp_ub(VSEP ? e[r] + vj[r] : e[r], tab);
                     if (MODE == 0) {
                         wl[r] = bcol[r] * l;
                         csum[r] = fma(brow[rt], l, csum[r]);
@@ -683,12 +683,12 @@ __device__ __forceinline__ void prep_work(const MMModel& md, const MMWork& wk, c
             const double* iKa = diag ? md.iK + mm_ik_blk(md, a) * npad * npad : nullptr;
             const PairOps po = pair_ops(wk, D, npad, pl, pair_col_block(wk, pl, b));
             if (fplds && mm_kp(DT) <= 16) {
-                if (diag) val = pair_wave<KCP, true, VSP, true, true>(po, Al, Bl, vl, beta_a, beta_b, iKa, tab, npad, i0, jb, je, lane, 64, 256, i0 - i_begin);
-                else val = pair_wave<KCP, false, VSP, true, true>(po, Al, Bl, vl, beta_a, beta_b, nullptr, tab, npad, i0, jb, je, lane, 64, 256, i0 - i_begin);
+                if (diag) val = pair_wave<KCP, true, VSP, true, true, false>(po, Al, Bl, vl, beta_a, beta_b, iKa, tab, npad, i0, jb, je, lane, 64, 256, i0 - i_begin);
+                else val = pair_wave<KCP, false, VSP, true, true, false>(po, Al, Bl, vl, beta_a, beta_b, nullptr, tab, npad, i0, jb, je, lane, 64, 256, i0 - i_begin);
             } else if (diag) {
-                val = pair_wave<KCP, true, VSP, true>(po, nullptr, nullptr, nullptr, beta_a, beta_b, iKa, tab, npad, i0, jb, je, lane);
+                val = pair_wave<KCP, true, VSP, true, false, false>(po, nullptr, nullptr, nullptr, beta_a, beta_b, iKa, tab, npad, i0, jb, je, lane);
             } else {
-                val = pair_wave<KCP, false, VSP, true>(po, nullptr, nullptr, nullptr, beta_a, beta_b, nullptr, tab, npad, i0, jb, je, lane);
+                val = pair_wave<KCP, false, VSP, true, false, false>(po, nullptr, nullptr, nullptr, beta_a, beta_b, nullptr, tab, npad, i0, jb, je, lane);
             }
             for (int off = 32; off > 0; off >>= 1) val += __shfl_down(val, off);
         }

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(512, OCC2 ? 4 : 2) void k_mm_prep(MMModel md, MMWor
     }
     if (FUSED && SR && PK != 1 && wk.fuse_pair && !spare_wg) {   // one-launch small step: the pair phase's exp table, on its way during the link
         double* tabL = sm_all + glue_doubles + prep_region_doubles(DT);
-        for (int e = threadIdx.x; e < FEXP_TN; e += 512) tabL[e] = wk.exp_tab[e];
+        for (int e = threadIdx.x; e < FEXP_TN; e += 512) tabL[e] = fexp_table_unbias(wk.exp_tab[e], e);   // (fexp_ub: mm_device.h)
     }
     // (the link's results are stored by the first pair workgroup; handing that to an idle slot of the spare columns -- a
     // workgroup with nothing else to do -- measured 1-2 % SLOWER on every configuration: docs/dead_ends.md)
