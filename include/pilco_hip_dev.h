@@ -84,6 +84,17 @@ int pilco_get_pair_timing(pilco_ctx* ctx, float* ms_pair, int* n_pair_launches);
 /* Developer aid: the first call (out32 may be NULL) switches on phase timestamps inside the
  * prep / glue kernels (100 MHz wall clock); later calls copy the 32 slots of the last launch. */
 int pilco_debug_timestamps(pilco_ctx* ctx, unsigned long long* out32);
+/* Test aid: what the host planner chose for the last pilco_rollout / pilco_rollout_tape / pilco_rollout_grad* on this context
+ * (a batch: its lane 0).  Host bookkeeping only.  Copies the first min(n, 12) words:
+ *   [0] entry: 1 rollout, 2 value-and-gradient rollout
+ *   [1] step: 0 none, 1 fused head + pair launch, 2 one-launch small step, 3 three-kernel step,
+ *       4 fused heads with the RbfController's own launches, 5 peer exchange
+ *   [2] policy: 0 no RbfController, 1 RbfController inside the link, 2 RbfController as launches of its own
+ *   [3] DT of the operand kernel   [4] KP of the pair kernel (KC = KP / 4)   [5] vsep
+ *   [6] the step's O(N^2) work: 0/1/2 pair kernel variant, 3 inside the head, 4 reverse-sweep launch, 5 reverse sweep inside the head
+ *   [7] tape: 0 none, 1 plain, 2 Jacobian   [8] H   [9] npad
+ *   [10] reverse chain: 0 none, 1 device, 2 host   [11] LDS bytes of a k_rev_step workgroup (device chain) */
+int pilco_debug_last_route(const pilco_ctx* ctx, int* out, int n);
 /* per-workgroup (start, end) stamps of the last prep launch, n values (developer aid) */
 int pilco_debug_blocks(pilco_ctx* ctx, unsigned long long* out, int n);
 /* developer aid: raw copy of a work buffer (0 row operands At, 1 column operands Wt | vcol, 2 reverse-pass row moments, 3 column sums, 4 beta) */

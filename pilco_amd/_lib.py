@@ -108,6 +108,7 @@ SIGNATURES = {
     "pilco_get_pair_timing": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "pilco_debug_timestamps": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "pilco_debug_blocks": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
+    "pilco_debug_last_route": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "pilco_debug_buffer": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_long]),
     "pilco_debug_sk_boundary": (C.c_int, [C.c_int] * 8),
     "pilco_debug_sk_pair_waves": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
@@ -638,6 +639,15 @@ class Context:
         buf = (C.c_ulonglong * 64)()
         self._chk(self.lib.pilco_debug_timestamps(self.h, buf if read else None))
         return list(buf)
+
+    ROUTE_FIELDS = ("entry", "step", "policy", "DT", "KP", "vsep", "pair", "tape", "H", "npad", "chain", "rev_lds")
+
+    def last_route(self):
+        """What the host planner chose for the last rollout / gradient rollout (include/pilco_hip_dev.h: pilco_debug_last_route),
+        as a dict keyed by ROUTE_FIELDS."""
+        buf = (C.c_int * len(self.ROUTE_FIELDS))()
+        self._chk(self.lib.pilco_debug_last_route(self.h, buf, len(buf)))
+        return {name: int(buf[i]) for i, name in enumerate(self.ROUTE_FIELDS)}
 
     def debug_blocks(self, n):
         buf = (C.c_ulonglong * n)()

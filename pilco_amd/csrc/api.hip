@@ -880,6 +880,13 @@ int pilco_debug_buffer(pilco_ctx* ctx, int slot, int which, double* out, long n)
     return PILCO_OK;
 }
 
+int pilco_debug_last_route(const pilco_ctx* ctx, int* out, int n) {
+    if (!ctx || !out || n <= 0) return PILCO_E_SHAPE;
+    const int k = std::min(n, (int)PILCO_ROUTE_WORDS);
+    for (int i = 0; i < k; ++i) out[i] = ctx->route[i];
+    return PILCO_OK;
+}
+
 int pilco_debug_blocks(pilco_ctx* ctx, unsigned long long* out, int n) {
     if (!ctx || !ctx->dbg || !out || n <= 0 || n > PILCO_DBG_WORDS - 64) return PILCO_E_SHAPE;
     HIPCHK(hipStreamSynchronize(ctx->st));

@@ -4,8 +4,10 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <cmath>
@@ -25,6 +27,27 @@ struct ChainGraph {
 };
 
 struct PredictWork;   // predict.hip
+
+// Layout of the route record (pilco_debug_last_route): one int per word.
+enum RouteWord {
+    ROUTE_ENTRY = 0,     // 1 = rollout (pilco_rollout, pilco_rollout_tape), 2 = value-and-gradient rollout
+    ROUTE_STEP = 1,      // 0 = no dynamics step launched, 1 = fused head + pair launch, 2 = one-launch small step,
+                         // 3 = three-kernel step, 4 = fused heads with the policy GP's own launches, 5 = peer exchange
+    ROUTE_POLICY = 2,    // 0 = no RbfController, 1 = RbfController inside the link, 2 = RbfController as launches of its own
+    ROUTE_DT = 3,        // instantiation of the operand kernel (mm_prep_dt)
+    ROUTE_KP = 4,        // contraction depth of the pair kernel (MMWork::KP; KC = KP / 4)
+    ROUTE_VSEP = 5,      // v_j added after the contraction (mm_vsep)
+    ROUTE_PAIR = 6,      // the dynamics step's O(N^2) work: 0/1/2 = pair kernel variant (pilco_set_pair_kernel), 3 = inside the head
+                         // (small step), 4 = reverse-sweep launch (Jacobian tape), 5 = reverse sweep inside the head
+    ROUTE_TAPE = 7,      // 0 = none, 1 = plain tape, 2 = Jacobian tape
+    ROUTE_H = 8,         // horizon of the enqueued steps
+    ROUTE_NPAD = 9,      // padded point count of the dynamics model
+    ROUTE_CHAIN = 10,    // reverse chain of a gradient rollout: 0 = none, 1 = device (rev.hip), 2 = host (grad.hip)
+    ROUTE_REV_LDS = 11,  // device chain: LDS bytes of one k_rev_step workgroup (above 65536: the raised per-kernel limit)
+    PILCO_ROUTE_WORDS = 12,
+    ROUTE_STEP_FIRST = ROUTE_STEP,
+    ROUTE_STEP_LAST = ROUTE_NPAD,
+};
 
 struct Slot {
     ChainGraph g_fact, g_fitc, g_fitc_nlml;   // exact / FITC factorisation, the FITC training objective (the exact objective = the factorisation's graph + two eager launches)
@@ -140,6 +163,11 @@ struct pilco_ctx {
     std::vector<unsigned long long> graph_key;
     std::vector<std::pair<std::vector<unsigned long long>, hipGraphExec_t>> graph_cache;   // most recently used first (<= 4)
     bool use_graph = true;
+    // pilco_debug_last_route (pilco_hip_dev.h): what the host planner chose for the last rollout / gradient rollout.  Words
+    // ROUTE_STEP_FIRST..ROUTE_STEP_LAST are written while the steps are enqueued; a replayed graph restores them from
+    // route_of_graph (the words of the capture under the same key).
+    std::array<int, PILCO_ROUTE_WORDS> route{};
+    std::map<std::vector<unsigned long long>, std::array<int, PILCO_ROUTE_WORDS>> route_of_graph;
     bool inline_policy = true;   // an RbfController small enough is evaluated inside the link (2 launches per step instead of 4)
     bool fused = true;   // fused head: the serial link of step t runs inside the prep launch of step t+1 (2 launches per step)
     bool fuse_small = true;   // ... and, for models of at most 256 points, the pair sums too: ONE launch per step (prep_device.h)

@@ -678,6 +678,9 @@ int rollout_grad_begin(pilco_ctx* ctx, const pilco_policy* policy, const pilco_r
 int rollout_grad_finish(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, int H, double* reward,
                         PolicyAdj& pol, pilco_seed_fn seed_fn, void* seed_user, GradCall& gc) {
     const int E = policy->state_dim, U = policy->control_dim, D = E + U;
+    ctx->route[ROUTE_ENTRY] = 2;   // pilco_debug_last_route: the host chain
+    ctx->route[ROUTE_CHAIN] = 2;
+    ctx->route[ROUTE_REV_LDS] = 0;
     const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
     const bool jac = gc.jac;
     const bool timing = getenv("PILCO_GRAD_TIMING") != nullptr;   // developer aid: forward / reverse split on stderr
@@ -830,6 +833,9 @@ int rollout_grad_dev_begin(pilco_ctx* ctx, const pilco_policy* policy, const pil
 int rollout_grad_dev_finish(pilco_ctx* ctx, JtapeDev& dev, const pilco_policy* policy, int H, pilco_seed_fn seed_fn, void* seed_user,
                             double* reward, double* dW, double* db) {
     const int E = policy->state_dim, U = policy->control_dim;
+    ctx->route[ROUTE_ENTRY] = 2;   // pilco_debug_last_route: the device chain
+    ctx->route[ROUTE_CHAIN] = 1;
+    ctx->route[ROUTE_REV_LDS] = (int)rev_step_lds_bytes(E, U, E + U);
     if (int r = rollout_jtape_dev_finish(ctx, dev, H, E, seed_fn, seed_user)) return r;
     *reward = *dev.h_reward;
     memcpy(dW, dev.h_out, sizeof(double) * (size_t)U * E);

@@ -251,6 +251,7 @@ struct RevArgs {
     double* out;            // [U*E + U + 1 + E + E(E+1)/2 + 1]: dW | db | status (0 fine) | d / d (m_0, S_0 packed) | reward   (device-visible)
 };
 bool rev_chain_supported(int E, int U, int D);
+size_t rev_step_lds_bytes(int E, int U, int D);   // dynamic LDS of one k_rev_step workgroup
 size_t rev_loc_doubles(int E, int U);
 size_t rev_mat_doubles(int E, int U, int D);
 RevLocalArgs rev_local_args(int n, const RewardDev* rw, int E, int U, const double* traj, const double* Wp, const double* bp, const double* maxact,

@@ -376,6 +376,7 @@ bool rev_chain_supported(int E, int U, int D) {
            sizeof(double) * rev_step_lds_doubles(E, U, D) <= 160 * 1024;
 }
 
+size_t rev_step_lds_bytes(int E, int U, int D) { return sizeof(double) * rev_step_lds_doubles(E, U, D); }
 size_t rev_loc_doubles(int E, int U) { return (size_t)rev_loc_size(E, U); }
 RevLocalArgs rev_local_args(int n, const RewardDev* rw, int E, int U, const double* traj, const double* Wp, const double* bp, const double* maxact,
                             double* loc) {

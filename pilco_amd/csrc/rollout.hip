@@ -124,6 +124,8 @@ int setup_rollout(pilco_ctx* ctx, const pilco_policy* pol, const pilco_reward_te
     if (pol->kind < 0 || pol->kind > 2) return fail(ctx, PILCO_E_SHAPE, "rollout: unknown policy kind");
     if (n_rw < 0 || n_rw > MAX_REWARD_TERMS || (n_rw > 0 && !rw)) return fail(ctx, PILCO_E_SHAPE, "rollout: 0..4 reward terms supported");
     if (int r = build_work(ctx, s)) return r;
+    ctx->route.fill(0);
+    ctx->route[ROUTE_ENTRY] = 1;
     // state: 2 x (m_x[E] s_x[E*E]) | s1[E*D] | reward[1]
     const size_t n_state = 2 * ((size_t)E + E * E) + 2 * (size_t)E * D + 1 + 8;
     ENSURE(ctx->state, n_state);
@@ -297,6 +299,21 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
     // Jacobian tape (bwd.hip): the dynamics step runs the reverse sweep in place of the forward pair kernel; the serial
     // link packs N_ab from the per-workgroup partials the sweep leaves in the tile-partial layout
     const bool jac = plan.jrec != nullptr;
+    auto& rt = ctx->route;   // pilco_debug_last_route: the branch taken below
+    rt[ROUTE_DT] = mm_prep_dt(s.D);
+    rt[ROUTE_KP] = s.wk.KP;
+    rt[ROUTE_VSEP] = s.wk.vsep ? 1 : 0;
+    rt[ROUTE_TAPE] = jac ? 2 : (g.tape ? 1 : 0);
+    rt[ROUTE_H] = H;
+    rt[ROUTE_NPAD] = s.npad;
+    rt[ROUTE_STEP] = 0;
+    rt[ROUTE_PAIR] = -1;
+    auto route = [&](int step, bool inline_pol, int pair) {
+        rt[ROUTE_STEP] = H > 0 ? step : 0;
+        rt[ROUTE_POLICY] = rbf ? (inline_pol ? 1 : 2) : 0;
+        rt[ROUTE_PAIR] = (s.wk.PL > 0 && H > 0) ? pair : -1;
+    };
+    const int pair_launch = jac ? 4 : ctx->variant;   // what dyn_pairs launches
     MMWork wk0 = s.wk;
     if (jac) {
         wk0.sk_waves = 0;
@@ -348,6 +365,7 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
         // geometry seen here must agree, or the finish would read the tape in the wrong layout
         if (jac && plan.jsmall > 0 && !small_ok) return fail(ctx, PILCO_E_STATE, "rollout: the planned one-launch small step does not fit the step's geometry");
         const bool small = jac ? (plan.jsmall > 0) : (small_ok && ctx->variant == 0);
+        route(small ? 2 : 1, rbf, small ? (jac ? 5 : 3) : pair_launch);
         if (small)
             for (int k = 0; k < 2; ++k) {
                 wkb[k].fuse_pair = jac ? 2 : 1;
@@ -413,6 +431,7 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
         // No host involvement and no collective launch per step; the state and s1 alternate between two buffers as in the
         // single-rank fused path.  The reward of state h is taken by head h (k_glue launches: by the launch that
         // propagates state h, from its pre-propagation copy), i.e. in the same order on every rank.
+        route(5, rbf, s.wk.PL > 0 ? ctx->variant : -1);
         PeerXch& x = ctx->xq;
         {   // executed now (not being captured into a graph): this rollout's epoch base goes up ahead of its launches
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -500,6 +519,7 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
         // four launches per step instead of six (two of them single-workgroup glue launches).  What a head's link reads
         // was written by EARLIER launches and what its prep part writes belongs to the other GP: no double buffering
         // beyond the state's.
+        route(4, false, pair_launch);
         size_t evi = 0;
         for (int h = 0; h < H; ++h) {
             GlueArgs ga = g;
@@ -553,6 +573,7 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
         ga.flags = keep;
     };
     const bool rbf_l = rbf && !inl_link;   // the policy GP as launches of its own (an inline policy is part of the link kernel)
+    route(3, !rbf_l, pair_launch);
     g.flags = GF_TRAJ | (H > 0 ? (rbf_l ? GF_RBF_PRE : GF_POLICY) : 0);
     launch_glue(ctx->st, g);
     if (rbf_l && H > 0) policy_stage(g);
@@ -622,6 +643,9 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
     if (!ctx->use_graph || lockstep || (sharded && (!ctx->comm || ctx->graph_rccl_failed)) || (ctx->dbg && !getenv("PILCO_DBG_GRAPH")))
         return enqueue_rollout(ctx, plan, H, nullptr);
     const GlueArgs& g = plan.g;
+    // (everything in the key is fixed before the launches are enqueued: enqueue_rollout_steps may clear plan.g.pol_inline when
+    // the step cannot take the inline policy, so the key holds the setting and the policy's eligibility, not that decision --
+    // a key that changed between the capture and the replay captured again and handed out the warm-up's one-step result)
     std::vector<unsigned long long> key = {
         (unsigned long long)H, (unsigned long long)g.pol_kind, (unsigned long long)g.n_rewards, (unsigned long long)g.squash,
         (unsigned long long)ctx->variant, (unsigned long long)ctx->fused + 2ull * (unsigned long long)ctx->fuse_small + 4ull * (unsigned long long)(ctx->share_cu != 0), (unsigned long long)(uintptr_t)plan.st[0], (unsigned long long)(uintptr_t)g.s1,
@@ -638,7 +662,7 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
         (unsigned long long)ctx->slot[1].wk.sk_waves, (unsigned long long)(uintptr_t)ctx->slot[1].w_small.p,
         (unsigned long long)(uintptr_t)ctx->slot[1].w_in.p, (unsigned long long)(uintptr_t)ctx->slot[1].ls.p,
         (unsigned long long)(peer ? 1 : 0), (unsigned long long)(uintptr_t)ctx->xq.local, (unsigned long long)ctx->nranks, (unsigned long long)ctx->rank,
-        (unsigned long long)(g.pol_inline && ctx->inline_policy ? 1 : 0), (unsigned long long)(uintptr_t)ctx->slot[1].var.p,
+        (unsigned long long)(ctx->inline_policy && g.pol_lds > 0 ? 1 : 0), (unsigned long long)(uintptr_t)ctx->slot[1].var.p,
         (unsigned long long)(uintptr_t)plan.jrec, (unsigned long long)plan.jstride, (unsigned long long)(uintptr_t)s.jac_rowmom.p,
         (unsigned long long)(uintptr_t)s.jac_cpart.p, (unsigned long long)(uintptr_t)s.jac_part.p, (unsigned long long)(uintptr_t)s.jac_head.p,
         (unsigned long long)(uintptr_t)s.jac_np.p};
@@ -656,6 +680,8 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
             if (i != 0) std::swap(ctx->graph_cache[i], ctx->graph_cache[0]);   // most recently used first
             ctx->graph = ctx->graph_cache[0].second;
             ctx->graph_key = key;
+            const auto rk = ctx->route_of_graph.find(key);
+            for (int w = ROUTE_STEP_FIRST; w <= ROUTE_STEP_LAST; ++w) ctx->route[w] = rk != ctx->route_of_graph.end() ? rk->second[w] : -1;
             if (peer) {
                 if (int r = xq_begin(ctx)) return r;
                 ctx->xq.epoch += (unsigned long long)H;
@@ -707,6 +733,8 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
         }
         ctx->graph_key = key;
         ctx->graph_cache.insert(ctx->graph_cache.begin(), std::make_pair(key, ctx->graph));
+        if (ctx->route_of_graph.size() >= 64) ctx->route_of_graph.clear();   // (keys of evicted graphs; bounded)
+        ctx->route_of_graph[key] = ctx->route;
         // the warm-up rollout above overwrote the initial state: the caller re-uploads it (see callers)
         return -1;
     }
@@ -746,13 +774,15 @@ static int rollout_begin(pilco_ctx* ctx, const pilco_policy* policy, const pilco
     double* pin_out = ctx->pin_io + nst;
     memcpy(pin_in, m0, sizeof(double) * E);
     memcpy(pin_in + E, S0, sizeof(double) * E * E);
+    int rr = -1;
     for (int attempt = 0; attempt < 2; ++attempt) {
         HIPCHK(hipMemcpyAsync(plan.st[0], pin_in, sizeof(double) * nst, hipMemcpyHostToDevice, ctx->st));
-        const int r = run_rollout(ctx, plan, H);
-        if (r == -1) continue;  // graph was just (re)captured: upload the state again and replay it
-        if (r != PILCO_OK) return r;
+        rr = run_rollout(ctx, plan, H);
+        if (rr == -1) continue;  // graph was just (re)captured: upload the state again and replay it
+        if (rr != PILCO_OK) return rr;
         break;
     }
+    if (rr == -1) return fail(ctx, PILCO_E_STATE, "rollout: the launch sequence was captured twice and never ran");
     HIPCHK(hipMemcpyAsync(pin_out, plan.st[H & 1], sizeof(double) * nst, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(pin_out + nst, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
     if (traj)
@@ -1084,14 +1114,16 @@ int pilco_rollout_tape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_r
     const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
     ENSURE(ctx->tape, std::max<size_t>(1, (size_t)H * TS));
     plan.g.tape = ctx->tape.p;
+    int rr = -1;
     for (int attempt = 0; attempt < 2; ++attempt) {   // replayed as a hipGraph like pilco_rollout (the tape pointer is part of the graph key)
         HIPCHK(hipMemcpyAsync(plan.st[0], m0, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
         HIPCHK(hipMemcpyAsync(plan.st[0] + E, S0, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
-        const int r = run_rollout(ctx, plan, H);
-        if (r == -1) continue;
-        if (r != PILCO_OK) return r;
+        rr = run_rollout(ctx, plan, H);
+        if (rr == -1) continue;
+        if (rr != PILCO_OK) return rr;
         break;
     }
+    if (rr == -1) return fail(ctx, PILCO_E_STATE, "rollout: the launch sequence was captured twice and never ran");
     HIPCHK(hipMemcpyAsync(mH, plan.st[H & 1], sizeof(double) * E, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(SH, plan.st[H & 1] + E, sizeof(double) * E * E, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(reward, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
@@ -1177,14 +1209,16 @@ int rollout_jtape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward
     plan.jsmall = sharded ? 0 : jac_small_chunks(ctx, plan, H);
     double* h_misc = dev ? h_traj + NTJ : h_jrec + (size_t)H * JSg;
     double* h_all = h_misc + 8;                          // sharded: [W][H][PLcap * recp | E * reco]
+    int rr = -1;
     for (int attempt = 0; attempt < 2; ++attempt) {
         HIPCHK(hipMemcpyAsync(plan.st[0], m0, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
         HIPCHK(hipMemcpyAsync(plan.st[0] + E, S0, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
-        const int r = run_rollout(ctx, plan, H);
-        if (r == -1) continue;
-        if (r != PILCO_OK) return r;
+        rr = run_rollout(ctx, plan, H);
+        if (rr == -1) continue;
+        if (rr != PILCO_OK) return rr;
         break;
     }
+    if (rr == -1) return fail(ctx, PILCO_E_STATE, "rollout: the launch sequence was captured twice and never ran");
     if (!dev) HIPCHK(hipMemcpyAsync(h_misc, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
     if (dev) {
         // ---- the reverse chain on the device (rev.hip): nothing but the reward, the gradient -- and, for a caller with
