@@ -95,6 +95,13 @@ int pilco_debug_timestamps(pilco_ctx* ctx, unsigned long long* out32);
  *   [7] tape: 0 none, 1 plain, 2 Jacobian   [8] H   [9] npad
  *   [10] reverse chain: 0 none, 1 device, 2 host   [11] LDS bytes of a k_rev_step workgroup (device chain) */
 int pilco_debug_last_route(const pilco_ctx* ctx, int* out, int n);
+/* Test aid: the step geometry of the dynamics slot's current workspace (after a rollout; host bookkeeping only).  Copies the
+ * first min(n, 14) words: [0] npad [1] local pairs PL [2] local outputs EL [3] operand row chunks NCH [4] mean row chunks NCHM
+ * [5] NT [6] stream-K waves (0: no stream-K cut) [7] stream-K steps T [8] diagonal pairs streaming iK [9] partial slots per pair
+ * [10] stream-K capacity of the pair kernel's instantiation (without PILCO_SK_WAVES) [11] CUs [12] / [13] column splits of
+ * the one-launch small step with / without a reward workgroup */
+#define PILCO_GEOMETRY_WORDS 14
+int pilco_debug_geometry(pilco_ctx* ctx, int* out, int n);
 /* per-workgroup (start, end) stamps of the last prep launch, n values (developer aid) */
 int pilco_debug_blocks(pilco_ctx* ctx, unsigned long long* out, int n);
 /* developer aid: raw copy of a work buffer (0 row operands At, 1 column operands Wt | vcol, 2 reverse-pass row moments, 3 column sums, 4 beta) */

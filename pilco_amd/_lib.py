@@ -109,6 +109,7 @@ SIGNATURES = {
     "pilco_debug_timestamps": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
     "pilco_debug_blocks": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
     "pilco_debug_last_route": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
+    "pilco_debug_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "pilco_debug_buffer": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_long]),
     "pilco_debug_sk_boundary": (C.c_int, [C.c_int] * 8),
     "pilco_debug_sk_pair_waves": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
@@ -648,6 +649,16 @@ class Context:
         buf = (C.c_int * len(self.ROUTE_FIELDS))()
         self._chk(self.lib.pilco_debug_last_route(self.h, buf, len(buf)))
         return {name: int(buf[i]) for i, name in enumerate(self.ROUTE_FIELDS)}
+
+    GEOMETRY_FIELDS = ("npad", "PL", "EL", "NCH", "NCHM", "NT", "sk_waves", "sk_total", "sk_nd", "sk_maxw", "sk_capacity", "cus",
+                       "NCS_reward", "NCS_no_reward")
+
+    def geometry(self):
+        """The step geometry of the dynamics slot's current workspace (include/pilco_hip_dev.h: pilco_debug_geometry), as a dict
+        keyed by GEOMETRY_FIELDS."""
+        buf = (C.c_int * len(self.GEOMETRY_FIELDS))()
+        self._chk(self.lib.pilco_debug_geometry(self.h, buf, len(buf)))
+        return {name: int(buf[i]) for i, name in enumerate(self.GEOMETRY_FIELDS)}
 
     def debug_blocks(self, n):
         buf = (C.c_ulonglong * n)()

@@ -69,19 +69,28 @@ int build_work(pilco_ctx* ctx, Slot& s) {
                 if (pl * W + rank < E) ++nd;
         if (no_iK) tdiag = toff;
         const long T = (long)nd * tdiag + (long)(wk.PL - nd) * toff;
-        int waves = mm_pair_sk_capacity(wk.KP, wk.vsep != 0);
-        if ((long)waves > T) waves = (int)std::max<long>(4, (T + 3) / 4 * 4);
+        auto cut = [&](int cap) { return (long)cap > T ? (int)std::max<long>(4, (T + 3) / 4 * 4) : cap; };
+        int waves = cut(mm_pair_sk_capacity(wk.KP, wk.vsep != 0, true));
+        int ud = 5, uo = 4;   // measured: a diagonal step (iK stream + one more FMA per element) costs ~5/4 of an off-diagonal one
+        if (const char* env = getenv("PILCO_SK_UNITS")) {
+            int a = 0, b = 0;
+            if (sscanf(env, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) { ud = a; uo = b; }
+        }
+        // a wave keeps the sums of at most two pairs (sk_wave_range): an override (PILCO_SK_WAVES / PILCO_SK_UNITS) under
+        // which some wave would touch three is refused for the computed cut; one step per wave if even that would
+        if (mm_sk_max_pairs(waves, nd, tdiag, toff, wk.PL, ud, uo) > 2) {
+            waves = cut(mm_pair_sk_capacity(wk.KP, wk.vsep != 0, false));
+            ud = 5;
+            uo = 4;
+            if (mm_sk_max_pairs(waves, nd, tdiag, toff, wk.PL, ud, uo) > 2) waves = (int)std::max<long>(4, (T + 3) / 4 * 4);
+        }
         wk.sk_waves = waves;
         wk.sk_total = (int)T;
         wk.sk_nd = nd;
         wk.sk_tdiag = tdiag;
         wk.sk_toff = toff;
-        wk.sk_ud = 5;   // measured: a diagonal step (iK stream + one more FMA per element) costs ~5/4 of an off-diagonal one
-        wk.sk_uo = 4;
-        if (const char* env = getenv("PILCO_SK_UNITS")) {
-            int a = 0, b = 0;
-            if (sscanf(env, "%d,%d", &a, &b) == 2 && a > 0 && b > 0) { wk.sk_ud = a; wk.sk_uo = b; }
-        }
+        wk.sk_ud = ud;
+        wk.sk_uo = uo;
         wk.sk_maxw = mm_sk_maxw(wk);
         wk.sk_pls = round_up(wk.PL, 16);
     }

@@ -175,10 +175,11 @@ int rbf_inline_lds_doubles(int state_dim, int control_dim, int bf);
 // variant 0 = MFMA stream-K, 1 = VALU (tiled), 2 = MFMA tiled (bits independent of the rank count)
 void launch_mm_pair(hipStream_t st, const MMModel& md, const MMWork& wk, int variant);
 // stream-K geometry: resident waves of the MFMA pair kernel for this KP, and the per-pair step counts
-int mm_pair_sk_capacity(int KP, bool vsep);
+int mm_pair_sk_capacity(int KP, bool vsep, bool allow_env = true);   // allow_env: PILCO_SK_WAVES may override
 void mm_pair_sk_steps(int npad, int* tdiag, int* toff);
 int mm_sk_boundary(int w, int waves, int nd_steps, int total, int ud, int uo);
 int mm_sk_maxw(const MMWork& wk);
+int mm_sk_max_pairs(int waves, int nd, int tdiag, int toff, int n_pairs, int ud, int uo);   // most local pairs one wave's range touches
 void mm_sk_pair_waves(int k, int waves, int nd, int tdiag, int toff, int total, int ud, int uo, int* wlo, int* fslot, int* whi);   // needs the sk_* geometry fields and PL
 void launch_glue(hipStream_t st, const GlueArgs& g, bool with_reward_block = false);
 size_t glue_lds_bytes(int E, int D);

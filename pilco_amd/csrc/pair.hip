@@ -70,6 +70,9 @@ int mm_sk_maxw(const MMWork& wk) {
 int mm_sk_boundary(int w, int waves, int nd_steps, int total, int ud, int uo) {
     return sk_boundary_of(w, waves, nd_steps, total, ud, uo);
 }
+int mm_sk_max_pairs(int waves, int nd, int tdiag, int toff, int n_pairs, int ud, int uo) {
+    return sk_max_pairs_per_wave(waves, nd, tdiag, toff, n_pairs, ud, uo);
+}
 void mm_sk_pair_waves(int k, int waves, int nd, int tdiag, int toff, int total, int ud, int uo, int* wlo, int* fslot, int* whi) {
     sk_pair_waves(k, waves, nd, tdiag, toff, total, ud, uo, *wlo, *fslot, *whi);
 }
@@ -232,8 +235,8 @@ static int sk_capacity_of() {
     return nb * cus * 4;
 }
 
-int mm_pair_sk_capacity(int KP, bool vsep) {
-    const char* env = getenv("PILCO_SK_WAVES");
+int mm_pair_sk_capacity(int KP, bool vsep, bool allow_env) {
+    const char* env = allow_env ? getenv("PILCO_SK_WAVES") : nullptr;
     if (env && atoi(env) >= 4) return atoi(env) / 4 * 4;
     switch (KP / 4) {
         case 1: return vsep ? sk_capacity_of<1, true>() : sk_capacity_of<1, false>();

@@ -310,6 +310,18 @@ __host__ __device__ inline void sk_pair_waves(int k, int waves, int nd, int tdia
     fslot = sk_boundary_of(wlo, waves, nd_steps, total, ud, uo) < S0 ? 1 : 0;   // a wave that starts before the pair holds it second
     whi = sk_wave_of(S1 - 1, waves, nd_steps, total, ud, uo);
 }
+// the most local pairs one wave's range touches (sk_wave_range keeps the sums of two): a cut that exceeds two loses sums
+inline int sk_max_pairs_per_wave(int waves, int nd, int tdiag, int toff, int n_pairs, int ud, int uo) {
+    const int nd_steps = nd * tdiag, total = nd_steps + (n_pairs - nd) * toff;
+    auto pair_of = [&](int step) { return step < nd_steps ? step / tdiag : nd + (step - nd_steps) / toff; };
+    int most = 0;
+    for (int w = 0; w < waves; ++w) {
+        const int b0 = sk_boundary_of(w, waves, nd_steps, total, ud, uo), b1 = sk_boundary_of(w + 1, waves, nd_steps, total, ud, uo);
+        const int n = pair_of(b1 - 1) - pair_of(b0) + 1;
+        if (b1 > b0 && n > most) most = n;
+    }
+    return most;
+}
 __device__ __forceinline__ int sk_boundary(const MMWork& wk, int w) {
     return sk_boundary_of(w, wk.sk_waves, wk.sk_nd * wk.sk_tdiag, wk.sk_total, wk.sk_ud, wk.sk_uo);
 }

@@ -666,6 +666,13 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
         (unsigned long long)(uintptr_t)plan.jrec, (unsigned long long)plan.jstride, (unsigned long long)(uintptr_t)s.jac_rowmom.p,
         (unsigned long long)(uintptr_t)s.jac_cpart.p, (unsigned long long)(uintptr_t)s.jac_part.p, (unsigned long long)(uintptr_t)s.jac_head.p,
         (unsigned long long)(uintptr_t)s.jac_np.p};
+    // the shapes themselves: buffers only grow (DevBuf::ensure), so a smaller or differently laid-out model keeps every address
+    // above -- an exact model after a sparse one with M = N keeps n and npad too, and would replay the graph that reads Zt
+    const Slot& ps = ctx->slot[PILCO_SLOT_POLICY];
+    for (long v : {(long)s.N, (long)s.M, (long)s.n, (long)s.npad, (long)s.Npad, (long)s.D, (long)s.E, (long)plan.U, (long)s.wk.PL,
+                   (long)s.wk.EL, (long)s.wk.P, (long)s.wk.sk_total, (long)s.wk.sk_nd, (long)s.ignore_iK, (long)ps.n, (long)ps.npad,
+                   (long)ps.D, (long)ps.E, (long)ps.M})
+        key.push_back((unsigned long long)v);
     for (int i = 0; i < g.n_rewards; ++i) {
         key.push_back((unsigned long long)g.rw[i].kind);
         key.push_back((unsigned long long)(long long)g.rw[i].rank);
@@ -1416,3 +1423,16 @@ int rollout_jtape_wait(pilco_ctx* ctx, int t) {
     return PILCO_OK;
 }
 
+
+// test aid (pilco_debug_geometry): the step geometry of the dynamics slot's current workspace
+int pilco_debug_geometry(pilco_ctx* ctx, int* out, int n) {
+    if (!ctx || !out || n <= 0) return PILCO_E_SHAPE;
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    if (!s.wk_valid) return fail(ctx, PILCO_E_STATE, "debug_geometry: the dynamics slot has no step workspace (run a rollout first)");
+    const MMWork& wk = s.wk;
+    const int sk_cap = (ctx->variant == 0 && wk.PL > 0) ? mm_pair_sk_capacity(wk.KP, wk.vsep != 0, false) : 0;
+    const int v[PILCO_GEOMETRY_WORDS] = {s.npad, wk.PL, wk.EL, wk.NCH, wk.NCHM, wk.NT, wk.sk_waves, wk.sk_total, wk.sk_nd, wk.sk_maxw,
+                                         sk_cap, device_cus_of(ctx->device), small_col_splits(ctx, s, true), small_col_splits(ctx, s, false)};
+    for (int i = 0; i < std::min(n, (int)PILCO_GEOMETRY_WORDS); ++i) out[i] = v[i];
+    return PILCO_OK;
+}

@@ -56,8 +56,11 @@ def _trajectory(step, c, d):
     return np.stack(rows), total
 
 
-def oracle_trajectory(c, d):
+def oracle_trajectory(c, d, zero_iK=False):
+    """zero_iK: the model of gp_set_factors(iK=None, beta) -- the pair sums without the iK term."""
     iK, beta = factors(c, d)
+    if zero_iK:
+        iK = np.zeros_like(iK)
     pts = points(c, d)
     return _trajectory(lambda m, s: tp.predict_given_factorizations_pairs(pts, d["ls"], d["var"], m, s, iK, beta), c, d)
 
@@ -126,12 +129,14 @@ def block_error(dev, ref):
     return float(np.abs(dev - ref).max() / (scale if scale > 0 else 1.0)) if ref.size else 0.0
 
 
-def torch_gradient(c, d):
+def torch_gradient(c, d, zero_iK=False):
     """(reward, [d parameter] ) by torch autograd: (dW, db) for a LinearController, (d centres, d targets, d lengthscales)
-    for an RbfController."""
+    for an RbfController.  zero_iK: as in oracle_trajectory."""
     import torch
     from oracle import torch_path as tq
     iK, beta = factors(c, d)
+    if zero_iK:
+        iK = np.zeros_like(iK)
     pts, U = points(c, d), c["U"]
     gp = lambda m, s: tq.predict_given_factorizations(pts, d["ls"], d["var"], m, s, iK, beta)
     if c["policy"] == "linear":
