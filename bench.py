@@ -6,7 +6,13 @@ One "step" = one rollout = one PILCO.predict(m0, S0, H=40) (pilco.py:118-136) wi
 the GP factorisation cached on the device ("R-fwd" of SURVEY.md 8(d)); inputs are
 resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--no-secondary] [--no-cpu-baseline]]
+
+A plain run does what the headline needs and nothing else: it sets up (data, hyper-parameters, one factorisation),
+runs W untimed and K timed rollouts, writes the last one's outputs (--dump-outputs) and prints the result line.
+--full measures and checks the rest after the timed steps: the timed rollout against the executed reference
+(`verified`), the pair kernel's roofline, the other BASELINE configurations (`secondary`) and the CPU baseline; with
+N > 1 the other exchange, the unsharded replicas, per-rank phases and the Amdahl model.
 
 N > 1: launched under torch.distributed.run, one rank per GPU.  torch is used only
 to rendezvous (gloo: broadcast of the RCCL unique id and of the peer-exchange
@@ -460,13 +466,41 @@ def dump_outputs(out_dir, mH, SH, reward):
         np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
+def headline(args, world, ms_per_rollout, per_call, exchange):
+    """The result line as a plain run prints it, from the timed steps alone; --full adds its keys after these."""
+    return {
+        "metric": "moment-matching rollouts/sec (N=1000,D=10,E=10,H=40)",
+        "value": 1e3 / ms_per_rollout,
+        "unit": "rollouts/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_rollout,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: N=1000 D=10 E=10 H=40 full rollout + reward, "
+                               "control_dim=0 (D==E read literally), ExponentialReward(W=I,t=0), "
+                               "factorisation cached (R-fwd); one step = one host-synchronised pilco_rollout call "
+                               "(what PILCO.predict makes) with its result downloaded",
+                   "parallelism": "pairs%d" % world, "exchange": exchange,
+                   "median_ms_per_call": float(np.median(per_call)), "min_ms_per_call": float(np.min(per_call)),
+                   "max_ms_per_call": float(np.max(per_call))},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also verify the rollout against the executed reference and measure the roofline, "
+                         "the other configurations and the CPU baseline (a plain run prints the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip `secondary` (the other configurations, 1 GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (m_H, S_H, reward; float64) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -605,9 +639,15 @@ def main():
 
     wall_ms, per_call, (mH, SH, rew) = timed_leg()
     ms_per_rollout = wall_ms / args.steps
-    verified = verify_against_reference(mH, SH, float(rew[0, 0])) if rank == 0 else None
+    verified = verify_against_reference(mH, SH, float(rew[0, 0])) if rank == 0 and args.full else None
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, mH, SH, rew)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, ms_per_rollout, per_call, exchange)))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # dominant kernel (pair kernel): its own HIP-event pairs on the launch stream, separate pass
     prof = ctx.rollout_timed(policy, rewards, cfg["m0"], cfg["S0"], H, 1, time_pair=True)
@@ -730,26 +770,8 @@ def main():
                       "measured_rollouts_per_s": 1e3 / ms_per_rollout,
                       "exchange_and_skew_us_per_step": ms_per_rollout * 1e3 / H - pred_step,
                       "ideal_linear_rollouts_per_s": world * 1e3 / t1}
-        out = {
-            "metric": "moment-matching rollouts/sec (N=1000,D=10,E=10,H=40)",
-            "value": 1e3 / ms_per_rollout,
-            "unit": "rollouts/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_rollout,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: N=1000 D=10 E=10 H=40 full rollout + reward, "
-                                   "control_dim=0 (D==E read literally), ExponentialReward(W=I,t=0), "
-                                   "factorisation cached (R-fwd); one step = one host-synchronised pilco_rollout call "
-                                   "(what PILCO.predict makes) with its result downloaded",
-                       "parallelism": "pairs%d" % world, "exchange": exchange,
-                       "median_ms_per_call": float(np.median(per_call)), "min_ms_per_call": float(np.min(per_call)),
-                       "max_ms_per_call": float(np.max(per_call))},
+        out = headline(args, world, ms_per_rollout, per_call, exchange)
+        out.update({
             "verified": verified,
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
@@ -769,7 +791,7 @@ def main():
                          "gexp_per_s": exps / world / (pair_ms * 1e-3) / 1e9 if pair_ms > 0 else 0.0,
                          "algorithmic_bytes_per_launch": byts / world,
                          "hbm_GBps_algorithmic": byts / world / (pair_ms * 1e-3) / 1e9 if pair_ms > 0 else 0.0},
-        }
+        })
         if world == 1 and not args.no_secondary:
             out["secondary"] = secondary_metrics(ctx, cfg, policy, rewards, ms_per_rollout, args.steps)
             try:

@@ -15,7 +15,7 @@ with the synthetic inputs of pilco_amd/synthetic.py.  The loop be
 reference's tf.while_loop (pilco.py:126-135) written out so that every intermediate state can be stored;
 PILCO.predict itself is run for n = 2 beside it to show they are the same computation.  Stored: the state
 after every step and the running reward -- a few kB per configuration (tests/golden/c2_rollout*.npz).
-bench.py checks the (m_H, S_H, reward) it timed against c2_rollout.npz before printing its JSON line.
+bench.py --full checks the (m_H, S_H, reward) it timed against c2_rollout.npz before printing its JSON line.
 """
 from __future__ import annotations
 

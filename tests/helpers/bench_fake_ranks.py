@@ -1,7 +1,9 @@
 """Run bench.py's control flow (argument handling, gloo rendezvous, id broadcast, barriers, max-over-ranks timing, the
 replica leg, verification, the JSON line) with the device replaced by a stand-in Context, one process per rank on the
 CPU.  TEST HELPER (tests/test_sharding_cpu.py launches it under torch.distributed.run): the multi-rank branch of
-bench.py cannot run on the single-GPU test box, so its host logic is exercised here."""
+bench.py cannot run on the single-GPU test box, so its host logic is exercised here.  FAKE_CALLS=<path>: every rank
+writes the stand-in calls it received to <path>.<rank> as JSON when it ends."""
+import json
 import os
 import sys
 import time
@@ -24,6 +26,7 @@ class FakeContext:
     def __init__(self, device=None):
         self.device = device
         self.rank, self.nranks = 0, 1
+        FakeContext.calls.append(("context", device))
 
     def comm_unique_id(self):
         return bytes(range(128))
@@ -71,10 +74,12 @@ class FakeContext:
     def rollout(self, policy, rewards, m0, S0, H, want_traj=False):
         if self.attached and os.environ.get("FAKE_PEER") == "first_rollout_fails" and self.rank == 1:
             raise _lib.PilcoError(5, "rollout: peer exchange 1 timed out on rank 1 (stand-in)")
+        FakeContext.calls.append(("rollout", self.rank))
         time.sleep(0.002 * (1 + self.rank))            # ranks differ: the reported time must be the slowest one's
         return G["M_traj"][:, -1][None, :].copy(), G["S_traj"][:, :, -1].copy(), np.array([[G["R_traj"][-1]]])
 
     def rollout_timed(self, policy, rewards, m0, S0, H, reps, time_pair=True):
+        FakeContext.calls.append(("rollout_timed", self.rank))
         return dict(ms_total=2.6 * reps, ms_pair=0.047 * H, n_pair_launches=H)
 
     def close(self):
@@ -85,4 +90,9 @@ _lib.Context = FakeContext
 bench.engine_clock_under_pair_load = lambda *a, **k: (2000.0, 45.0)
 
 if __name__ == "__main__":
-    bench.main()
+    try:
+        bench.main()
+    finally:
+        if os.environ.get("FAKE_CALLS") and FakeContext.calls:   # (a process that only starts the ranks made no calls)
+            with open("%s.%s" % (os.environ["FAKE_CALLS"], os.environ.get("RANK", "0")), "w") as f:
+                json.dump(FakeContext.calls, f)

@@ -1994,10 +1994,10 @@ def test_policy_gradient_wide_inputs_vs_autograd(ctx, dims):
 
 @pytest.mark.parametrize("world", [2, 3, 4])
 def test_bench_ranks_in_separate_processes_peer_exchange_on_one_gpu(world):
-    """bench.py --gpus N exactly as the driver launches it (torch.distributed.run, one PROCESS per rank), all ranks on
+    """bench.py --gpus N --full exactly as the driver launches it (torch.distributed.run, one PROCESS per rank), all ranks on
     this box's single GPU (PILCO_BENCH_SHARE_GPU=1: RCCL refuses duplicate devices, so the beta rows travel over gloo): the
     sharded factorisation, the hipIpc-mapped exchange areas, the flag waits between processes and the graph replay of the
-    sharded rollout; bench.py itself verifies the rollout against the executed-reference fixture and reports the exchange
+    sharded rollout; bench.py --full itself verifies the rollout against the executed-reference fixture and reports the exchange
     it used.  world <= 4: with this process and the launcher that is six processes on the GPU, the most a shared machine
     takes at once; BASELINE config 3's eight ranks run as contexts of one process in test_sharded_rollout_group_of_contexts."""
     import json
@@ -2009,7 +2009,7 @@ def test_bench_ranks_in_separate_processes_peer_exchange_on_one_gpu(world):
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1", "--full"]
     env = dict(os.environ, PILCO_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=420, env=env, cwd=root)
     assert pr.returncode == 0, (pr.stdout[-1500:], pr.stderr[-3000:])
@@ -2018,6 +2018,31 @@ def test_bench_ranks_in_separate_processes_peer_exchange_on_one_gpu(world):
     d = json.loads(lines[0])
     assert d["n_gpus"] == world and "peer stores" in d["config"]["exchange"], d["config"]
     assert d["verified"]["max_rel_err"]["S_H"] < 1e-5 and d["verified"]["max_rel_err"]["reward"] < 1e-5
+
+
+def test_bench_plain_run_outputs_match_the_executed_reference(tmp_path):
+    """A plain `bench.py --gpus 1` (no --full) on the device: the result line's own keys only, and what its last timed step
+    returned -- written by --dump-outputs -- within the 1e-5 relative tolerance of the executed-reference fixture that
+    `bench.py --full` checks it against."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    pr = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=root)
+    assert pr.returncode == 0, (pr.stdout[-1500:], pr.stderr[-3000:])
+    lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, pr.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert list(d) == ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                       "vs_baseline", "dtype", "data", "config"]
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-9
+    g = np.load(os.path.join(root, "tests", "golden", "c2_rollout.npz"))
+    np.testing.assert_allclose(np.load(str(tmp_path / "m_H.npy")), g["M_traj"][:, -1][None, :], rtol=1e-5, atol=0)
+    np.testing.assert_allclose(np.load(str(tmp_path / "S_H.npy")), g["S_traj"][:, :, -1], rtol=1e-5, atol=0)
+    np.testing.assert_allclose(np.load(str(tmp_path / "reward.npy")), [[float(g["R_traj"][-1])]], rtol=1e-5, atol=0)
 
 
 @pytest.mark.parametrize("D", [3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 14])

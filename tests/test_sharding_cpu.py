@@ -180,7 +180,7 @@ def test_stream_k_closed_forms_match_enumeration():
 
 @pytest.mark.parametrize("peer", ["ok", "rank1_fails", "first_rollout_fails"])
 def test_bench_multi_rank_host_logic_under_torchrun(peer):
-    """bench.py --gpus 2 exactly as the driver launches it (python -m torch.distributed.run, one process per rank), with
+    """bench.py --gpus 2 --full exactly as the driver launches it (python -m torch.distributed.run, one process per rank), with
     the device replaced by a stand-in Context (tests/helpers/bench_fake_ranks.py): rendezvous over gloo on 127.0.0.1,
     broadcast of rank 0's RCCL id, barriers, MAX-over-ranks timing, the replica leg, verification against the fixture and
     ONE JSON line from rank 0 with the contract's keys.  The per-step exchange: peer exchange when every rank attaches and
@@ -192,7 +192,7 @@ def test_bench_multi_rank_host_logic_under_torchrun(peer):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "tests", "helpers", "bench_fake_ranks.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", FAKE_PEER=peer)
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert pr.returncode == 0, pr.stderr[-2000:]
@@ -228,13 +228,14 @@ def test_bench_multi_rank_host_logic_under_torchrun(peer):
 
 def test_bench_gpus_2_invoked_plainly_starts_its_own_ranks():
     """`python bench.py --gpus 2 ...` typed the way the driver types the 1-GPU line (no launcher, WORLD_SIZE unset): the
-    script re-executes itself under torch.distributed.run with one process per rank and rank 0 prints the ONE JSON line
-    (round-3 review, missing #1: it used to exit with a usage message)."""
+    script re-executes itself under torch.distributed.run with one process per rank, its options (--full here) go along, and
+    rank 0 prints the ONE JSON line (round-3 review, missing #1: it used to exit with a usage message)."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(OMP_NUM_THREADS="1", FAKE_PEER="ok")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "helpers", "bench_fake_ranks.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "helpers", "bench_fake_ranks.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--full"]
     pr = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
@@ -242,3 +243,84 @@ def test_bench_gpus_2_invoked_plainly_starts_its_own_ranks():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["secondary"]["rccl_comm_count"] == 2
     assert "peer stores" in d["config"]["exchange"] and "RCCL" in d["secondary"]["other_exchange"]["exchange"]
+
+
+HEADLINE = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config"]
+
+
+def _fake_bench(tmp_path, args, ranks=1, peer="ok"):
+    """bench.py on the stand-in Context (one process, or `ranks` processes under torch.distributed.run): its ONE JSON line
+    and, per rank, the stand-in calls in the order they were made."""
+    import json
+    import subprocess
+    helper = os.path.join(ROOT, "tests", "helpers", "bench_fake_ranks.py")
+    if ranks == 1:
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+        cmd = [sys.executable, helper, "--gpus", "1"] + args
+    else:
+        env = dict(os.environ)
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr",
+               "127.0.0.1", "--master-port", str(port), helper, "--gpus", str(ranks)] + args
+    env.update(OMP_NUM_THREADS="1", FAKE_PEER=peer, FAKE_CALLS=str(tmp_path / "calls"))
+    pr = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+    assert pr.returncode == 0, pr.stderr[-2000:]
+    lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, pr.stdout[-2000:]
+    calls = [[tuple(c) for c in json.load(open(str(tmp_path / "calls") + ".%d" % r))] for r in range(ranks)]
+    return json.loads(lines[0]), calls
+
+
+def _assert_headline(d, world, steps, warmup, min_ms):
+    assert list(d)[:len(HEADLINE)] == HEADLINE
+    assert d["metric"] == "moment-matching rollouts/sec (N=1000,D=10,E=10,H=40)" and d["unit"] == "rollouts/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["scaling"] == "strong" and d["vs_baseline"] is None
+    assert d["n_gpus"] == world and d["steps"] == steps and d["warmup"] == warmup
+    assert d["ms_per_step"] >= min_ms and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-9
+    assert d["config"]["parallelism"] == "pairs%d" % world
+
+
+def test_bench_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    """A plain `bench.py --gpus 1` (no --full): one context, one factorisation, the warm-up and the timed rollouts, the last
+    one's outputs written as they were returned, and the result line's own keys only -- no check against the reference, no
+    roofline pass, no other configuration, no CPU baseline."""
+    d, (calls,) = _fake_bench(tmp_path, ["--steps", "4", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")])
+    assert list(d) == HEADLINE
+    _assert_headline(d, 1, 4, 2, min_ms=2.0)                 # the stand-in sleeps 2 ms per rollout
+    assert d["config"]["exchange"] == "none (one rank)"
+    assert calls == [("context", 0), ("factorize", 0, 1)] + [("rollout", 0)] * 6
+    G = np.load(os.path.join(ROOT, "tests", "golden", "c2_rollout.npz"))
+    for name, want in (("m_H", G["M_traj"][:, -1][None, :]), ("S_H", G["S_traj"][:, :, -1]), ("reward", np.array([[G["R_traj"][-1]]]))):
+        got = np.load(str(tmp_path / "out" / (name + ".npy")))
+        assert got.dtype == np.float64 and got.shape == want.shape and np.array_equal(got, want), name
+
+
+def test_bench_full_run_adds_its_keys_after_the_timed_steps(tmp_path):
+    """`bench.py --gpus 1 --full` (the other configurations and the CPU baseline left out, they need the device): the same
+    headline from the same calls, then the check against the executed reference and the pair kernel's own timing pass."""
+    d, (calls,) = _fake_bench(tmp_path, ["--steps", "3", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline",
+                                         "--dump-outputs", str(tmp_path / "out")])
+    assert list(d) == HEADLINE + ["verified", "roofline"]
+    _assert_headline(d, 1, 3, 1, min_ms=2.0)
+    assert d["verified"]["max_rel_err"]["S_H"] == 0.0 and d["verified"]["rtol"] == 1e-5
+    assert abs(d["roofline"]["avg_launch_ms"] - 0.047) < 1e-12 and d["roofline"]["engine_clock_mhz_under_load"] == 2000.0
+    assert calls == [("context", 0), ("factorize", 0, 1)] + [("rollout", 0)] * 4 + [("rollout_timed", 0)]
+    assert os.path.exists(str(tmp_path / "out" / "S_H.npy"))
+
+
+@pytest.mark.parametrize("peer", ["ok", "first_rollout_fails"])
+def test_bench_plain_multi_rank_run_prints_the_headline_only(tmp_path, peer):
+    """A plain `bench.py --gpus 2`: the exchange is still chosen before anything is timed (peer exchange, or RCCL after its
+    first rollout failed), the time is still the slowest rank's, and nothing runs after the timed steps: no second
+    exchange, no replica contexts, no timing pass, no verification."""
+    d, calls = _fake_bench(tmp_path, ["--steps", "3", "--warmup", "1"], ranks=2, peer=peer)
+    assert list(d) == HEADLINE
+    _assert_headline(d, 2, 3, 1, min_ms=4.0)                 # the slower rank (2 x 2 ms sleep) sets the time
+    assert ("peer stores" in d["config"]["exchange"]) == (peer == "ok"), d["config"]["exchange"]
+    for r, c in enumerate(calls):
+        # the first rollout over the peer exchange (rank 1's fails: every rank detaches), then warm-up + timed steps
+        first = [("rollout", r)] if peer == "ok" else [("rollout", r)] * (r == 0) + [("peer_detach", r)]
+        assert c == [("context", r), ("comm_init", r, 2), ("factorize", r, 2)] + first + [("rollout", r)] * 4, c

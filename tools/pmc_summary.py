@@ -19,7 +19,7 @@ for d in ("pmc_fetch", "pmc_write", "pmc_sq"):
 kern = {k: {c: v[1] / v[0] for c, v in cs.items()} for k, cs in acc.items()}
 pair = next((k for k in kern if "k_mm_pair_sk" in k), None)
 out = {
-    "command": "python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary (rocprofv3 --kernel-trace --pmc <one counter group per pass>; tools/profile_round.sh)",
+    "command": "python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary (rocprofv3 --kernel-trace --pmc <one counter group per pass>; tools/profile_round.sh)",
     "note": ("per-launch averages. FETCH_SIZE / WRITE_SIZE are KiB. Calibration on this access pattern (8 B/lane coalesced): "
              "k_matvec (non-transposed pass) reads 81920 KiB and reports FETCH_SIZE of about half that (the gfx950 under-count of "
              "MI355X_MICROARCH.md section HBM); k_gram writes 81920 KiB and reports WRITE_SIZE 81920 (1:1). "
