@@ -7,7 +7,6 @@
 #include <array>
 #include <chrono>
 #include <condition_variable>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <cmath>
@@ -45,9 +44,8 @@ enum RouteWord {
     ROUTE_CHAIN = 10,    // reverse chain of a gradient rollout: 0 = none, 1 = device (rev.hip), 2 = host (grad.hip)
     ROUTE_REV_LDS = 11,  // device chain: LDS bytes of one k_rev_step workgroup (above 65536: the raised per-kernel limit)
     PILCO_ROUTE_WORDS = 12,
-    ROUTE_STEP_FIRST = ROUTE_STEP,
-    ROUTE_STEP_LAST = ROUTE_NPAD,
 };
+enum StepKind { STEP_NONE = 0, STEP_FUSED = 1, STEP_SMALL = 2, STEP_THREE = 3, STEP_FUSED_RBF = 4, STEP_PEER = 5 };   // ROUTE_STEP
 
 struct Slot {
     ChainGraph g_fact, g_fitc, g_fitc_nlml;   // exact / FITC factorisation, the FITC training objective (the exact objective = the factorisation's graph + two eager launches)
@@ -163,11 +161,9 @@ struct pilco_ctx {
     std::vector<unsigned long long> graph_key;
     std::vector<std::pair<std::vector<unsigned long long>, hipGraphExec_t>> graph_cache;   // most recently used first (<= 4)
     bool use_graph = true;
-    // pilco_debug_last_route (pilco_hip_dev.h): what the host planner chose for the last rollout / gradient rollout.  Words
-    // ROUTE_STEP_FIRST..ROUTE_STEP_LAST are written while the steps are enqueued; a replayed graph restores them from
-    // route_of_graph (the words of the capture under the same key).
+    // pilco_debug_last_route (pilco_hip_dev.h): what the host planner chose for the last rollout / gradient rollout (the
+    // rollout's words are written from its StepRoute, eager or replayed alike)
     std::array<int, PILCO_ROUTE_WORDS> route{};
-    std::map<std::vector<unsigned long long>, std::array<int, PILCO_ROUTE_WORDS>> route_of_graph;
     bool inline_policy = true;   // an RbfController small enough is evaluated inside the link (2 launches per step instead of 4)
     bool fused = true;   // fused head: the serial link of step t runs inside the prep launch of step t+1 (2 launches per step)
     bool fuse_small = true;   // ... and, for models of at most 256 points, the pair sums too: ONE launch per step (prep_device.h)
@@ -266,6 +262,15 @@ int pilco_factorize_fitc(pilco_ctx* ctx, void* slot_ptr);
 void predict_release(Slot& s);   // frees Slot::pred
 
 // rollout.hip
+// The route of one rollout, decided before anything is enqueued (plan_route): every launch of the rollout follows it, its
+// graph key holds it and the route record is written from it.
+struct StepRoute {
+    int step = STEP_NONE;   // ROUTE_STEP: the step structure (STEP_NONE: H = 0, the three-kernel step's first glue launch only)
+    int policy = 0;         // ROUTE_POLICY (inside the link: the fused head, over the peer exchange too, or the three-kernel step's link kernel)
+    int pair = -1;          // ROUTE_PAIR
+    int ncs = 0;            // STEP_SMALL: column splits of a pair (MMWork::NCS); 0 otherwise
+    bool timed = false;     // event pairs (ctx->pair_events) around the O(N^2) launches: never the one-launch small step
+};
 struct RolloutPlan {
     GlueArgs g{};
     double* st[2] = {nullptr, nullptr};  // double-buffered state: m_x[E] | s_x[E*E]
@@ -273,7 +278,7 @@ struct RolloutPlan {
     int E = 0, D = 0, U = 0;
     double* jrec = nullptr;              // Jacobian tape (bwd.hip): the dynamics step runs launch_mm_jac and writes jrec[t]
     size_t jstride = 0;
-    int jsmall = 0;                      // > 0: the steps of this value-and-gradient rollout run as the one-launch small step (chunks per pair)
+    StepRoute route;
 };
 constexpr int PILCO_JAC_TOO_LARGE = -77;   // rollout_jtape: the per-step buffers would exceed the cap (caller falls back)
 // Device reverse chain of a LinearController's gradient: what rollout_jtape(.., dev) leaves enqueued / staged.
@@ -302,8 +307,6 @@ struct LanesGuard {
 };
 int setup_rollout(pilco_ctx* ctx, const pilco_policy* pol, const pilco_reward_term* rw, int n_rw, int H, bool want_traj,
                   RolloutPlan& plan);
-int enqueue_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H, std::vector<hipEvent_t>* pair_ev);
-int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H);
 // shard.hip: peer exchange
 void launch_peer_wait(hipStream_t st, unsigned long long* area, int k, int W, int spin);
 int peer_detach(pilco_ctx* ctx);

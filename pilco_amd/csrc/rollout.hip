@@ -153,8 +153,7 @@ int setup_rollout(pilco_ctx* ctx, const pilco_policy* pol, const pilco_reward_te
         g.pwk = ctx->slot[PILCO_SLOT_POLICY].wk;
         g.pvar = ctx->slot[PILCO_SLOT_POLICY].var.p;
         g.pmd = model_of(ctx->slot[PILCO_SLOT_POLICY]);
-        g.pol_lds = rbf_inline_lds_doubles(E, U, ctx->slot[PILCO_SLOT_POLICY].n);
-        g.pol_inline = (ctx->inline_policy && g.pol_lds > 0) ? 1 : 0;
+        g.pol_lds = rbf_inline_lds_doubles(E, U, ctx->slot[PILCO_SLOT_POLICY].n);   // (g.pol_inline: plan_route)
         for (int u = 0; u < U; ++u) hp[off + u] = pol->max_action ? pol->max_action[u] : 1.0;
         g.maxact = ctx->params.p + off; off += U;
     }
@@ -183,40 +182,6 @@ int setup_rollout(pilco_ctx* ctx, const pilco_policy* pol, const pilco_reward_te
     return PILCO_OK;
 }
 
-// The fused heads need the serial link's and the operand kernel's LDS side by side in one workgroup: wide models
-// (D > 24 with many outputs) exceed the CU's 160 KB and run the three-kernel step instead (same results).
-// The answer must be the SAME ON EVERY RANK (it selects between the peer exchange and the collective path, and ranks
-// that disagree wait for each other forever): it is computed from the model dimensions and the rank COUNT only -- the
-// geometry of rank 0, which holds the largest share of pairs and outputs under the round-robin dealing.
-static bool fused_heads_fit(pilco_ctx* ctx, const RolloutPlan& plan) {
-    const Slot& s = ctx->slot[0];
-    const bool rbf = plan.g.pol_kind == PILCO_POLICY_RBF;
-    GlueArgs gl = plan.g;
-    if (ctx->nranks > 1) {
-        const int W = ctx->nranks, P = s.E * (s.E + 1) / 2;
-        gl.wk.PL = (P + W - 1) / W;
-        gl.wk.EL = (s.E + W - 1) / W;
-        mm_prep_chunks(s.npad, std::max(gl.wk.PL, 1), gl.wk.EL, &gl.wk.NCH, &gl.wk.NCHM);
-    } else if (s.wk.PL <= 0) {
-        return true;
-    }
-    const bool rbf_k = rbf && !gl.pol_inline;   // the policy GP as launches of its own (an inline policy is part of the link)
-    gl.flags = GF_TRAJ | GF_POLICY | GF_PACK | GF_ASSEMBLE | GF_PROPAGATE | (rbf_k ? (GF_RBF_PRE | GF_RBF_POST) : 0);
-    const int rew_E = plan.g.n_rewards > 0 ? plan.E : 0;
-    bool fits = mm_fused_head_fits(model_of(s), rew_E, gl);
-    if (fits && rbf_k) fits = mm_fused_head_fits(model_of(ctx->slot[PILCO_SLOT_POLICY]), rew_E, gl);
-    return fits;
-}
-
-// The peer exchange carries a rollout when it is attached, the model is sharded, the policy is not an RbfController
-// (its GP is not sharded) and the segments fit the exchange slots; otherwise the RCCL / group path runs.
-static bool peer_rollout_applies(pilco_ctx* ctx, const RolloutPlan& plan, int H) {
-    const Slot& s = ctx->slot[0];
-    // (an RbfController rides along when it is evaluated inside the link: every rank evaluates the whole, unsharded policy)
-    return ctx->xq.ready && ctx->nranks > 1 && ctx->xq.W == ctx->nranks && H > 0 &&
-           (plan.g.pol_kind != PILCO_POLICY_RBF || plan.g.pol_inline) &&
-           s.wk.SEG <= ctx->xq.cap && !plan.g.tape && !plan.jrec && fused_heads_fit(ctx, plan);
-}
 // Host side of a rollout's exchanges: the epoch base goes up before the rollout's launches (outside any graph: the
 // value changes per replay), `n` exchanges are accounted for afterwards.
 static int xq_begin(pilco_ctx* ctx) {
@@ -227,16 +192,6 @@ static int xq_begin(pilco_ctx* ctx) {
     return PILCO_OK;
 }
 
-// enqueue one full rollout on the stream (initial state already in plan.st[0]); the final
-// state ends up in plan.st[H & 1].  The reward of state t (pilco.py:133) is evaluated by the
-// second workgroup of the glue launch that turns state t into state t+1.
-static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::vector<hipEvent_t>* pair_ev);
-// Jacobian tape: the sums, moments and records of steps [t0, t1) in two launches behind the chain (rollout_jtape enqueues
-// them per chunk of steps, last steps first, each followed by its download: the host's reverse sweep works on one chunk
-// while the device finishes the next)
-// Does a value-and-gradient rollout of this plan run its steps as the one-launch small step (small_sweep)?  Returns the
-// workgroups per pair (row chunks x column splits) or 0.  (The same conditions enqueue_rollout_steps applies, plus those of its fused-head branch.)
-static bool fused_heads_fit(pilco_ctx* ctx, const RolloutPlan& plan);
 static int device_cus_of(int device) {
     static int cached[64] = {};
     int& c = cached[device & 63];
@@ -258,16 +213,91 @@ static int small_col_splits(pilco_ctx* ctx, const Slot& s, bool rew) {
     if (forced > 0 && forced <= s.wk.NCH && (forced & (forced - 1)) == 0 && forced <= 4) ncs = forced;
     return ncs;
 }
-static int jac_small_chunks(pilco_ctx* ctx, const RolloutPlan& plan, int H) {
+
+// Decide the route of a rollout of H steps before anything is enqueued (`timed`: event pairs will bracket its O(N^2)
+// launches).  Sets plan.route, the policy evaluation it implies (plan.g.pol_inline) and the route record
+// (pilco_debug_last_route): the eager launches, the graph key and a replay all follow this one decision.
+static int plan_route(pilco_ctx* ctx, RolloutPlan& plan, int H, bool timed) {
     const Slot& s = ctx->slot[0];
-    const int D = s.D, dtk = D <= 4 ? 4 : D <= 6 ? 6 : D <= 8 ? 8 : D <= 10 ? 10 : D == 11 ? 11 : D <= 12 ? 12 : D <= 14 ? 14 : D <= 16 ? 16 : 32;
-    const bool rbf = plan.g.pol_kind == PILCO_POLICY_RBF;
-    if (!ctx->fuse_small || !ctx->fused || ctx->nranks != 1 || ctx->comm || s.wk.PL <= 0 || H <= 0 || ctx->time_pairs || MM_ABL(s.wk, 255)) return 0;
-    if (D > 14 || s.npad > 256 || s.npad / s.wk.NCH != 64 || s.wk.KP != mm_kp(dtk) || (s.wk.vsep != 0) != mm_vsep(dtk) || s.wk.KP > 16) return 0;
-    if (rbf && !plan.g.pol_inline) return 0;
-    if (!fused_heads_fit(ctx, plan)) return 0;
-    return s.wk.NCH * small_col_splits(ctx, s, plan.g.n_rewards > 0 && !MM_ABL(s.wk, 8));
+    const GlueArgs& g = plan.g;
+    const bool rbf = g.pol_kind == PILCO_POLICY_RBF, jac = plan.jrec != nullptr;
+    const bool one = ctx->nranks == 1 && !ctx->comm, steps = s.wk.PL > 0 && H > 0;
+    // The fused heads need the serial link's and the operand kernel's LDS side by side in one workgroup: wide models
+    // (D > 24 with many outputs) exceed the CU's 160 KB and run the three-kernel step instead (same results).
+    // The answer must be the SAME ON EVERY RANK (it selects between the peer exchange and the collective path, and ranks
+    // that disagree wait for each other forever): it is computed from the model dimensions and the rank COUNT only -- the
+    // geometry of rank 0, which holds the largest share of pairs and outputs under the round-robin dealing.
+    auto fits = [&](bool inline_pol) {
+        GlueArgs gl = g;
+        gl.pol_inline = inline_pol ? 1 : 0;
+        if (ctx->nranks > 1) {
+            const int W = ctx->nranks, P = s.E * (s.E + 1) / 2;
+            gl.wk.PL = (P + W - 1) / W;
+            gl.wk.EL = (s.E + W - 1) / W;
+            mm_prep_chunks(s.npad, std::max(gl.wk.PL, 1), gl.wk.EL, &gl.wk.NCH, &gl.wk.NCHM);
+        } else if (s.wk.PL <= 0) {
+            return true;
+        }
+        const bool rbf_k = rbf && !inline_pol;   // the policy GP as launches of its own (an inline policy is part of the link)
+        gl.flags = GF_TRAJ | GF_POLICY | GF_PACK | GF_ASSEMBLE | GF_PROPAGATE | (rbf_k ? (GF_RBF_PRE | GF_RBF_POST) : 0);
+        const int rew_E = g.n_rewards > 0 ? plan.E : 0;
+        return mm_fused_head_fits(model_of(s), rew_E, gl) &&
+               (!rbf_k || mm_fused_head_fits(model_of(ctx->slot[PILCO_SLOT_POLICY]), rew_E, gl));
+    };
+    // An RbfController small enough (GlueArgs::pol_lds) is evaluated inside the link: on one rank when the fused head runs
+    // the step (which makes it the LinearController's: two launches); on several ranks always -- the policy GP is never
+    // sharded (every rank holds all of it) and its own launches would deal its pairs over the ranks -- by the fused head
+    // over the peer exchange, or (value-and-gradient rollouts: the three-kernel step with the all-gather) by the link kernel.
+    const bool eligible = rbf && ctx->inline_policy && g.pol_lds > 0;
+    if (rbf && !one && !eligible)
+        return fail(ctx, PILCO_E_STATE, "rollout: several ranks run an RbfController only with the inline policy (at most 256 basis functions, see pilco_set_inline_policy)");
+    const bool inl = eligible && (!one || (ctx->fused && steps && fits(true)));
+    const bool fit = fits(inl);
+    StepRoute r;
+    int step = STEP_THREE;
+    if (one && ctx->fused && fit && steps && (!rbf || inl)) {
+        step = STEP_FUSED;
+        // Small models: the pair sums ride in the head launch (prep_device.h) -- one launch per step.  The head instantiated for
+        // this input dimension carries the pair arithmetic of ONE contraction depth (that of D = DT); the workgroup's rows must
+        // be whole 32-row groups and one thread per point must cover the columns.  Value-and-gradient rollouts (the Jacobian
+        // tape, D <= 14) take the same road when the workgroup's operands stay in LDS (64-row chunks, KP <= 16): the pair
+        // workgroups run the reverse sweep of their block (small_sweep).
+        const int dt = mm_prep_dt(s.D);
+        const bool small = ctx->fuse_small && !timed && !MM_ABL(s.wk, 255) && s.npad <= 256 && s.wk.KP == mm_kp(dt) &&
+                           (s.wk.vsep != 0) == mm_vsep(dt) &&
+                           (jac ? s.npad / s.wk.NCH == 64 && s.wk.KP <= 16 : (s.npad / s.wk.NCH) % 32 == 0 && ctx->variant == 0);
+        if (small) {
+            step = STEP_SMALL;
+            r.ncs = small_col_splits(ctx, s, g.n_rewards > 0 && !MM_ABL(s.wk, 8));
+        }
+    } else if (ctx->xq.ready && ctx->nranks > 1 && ctx->xq.W == ctx->nranks && H > 0 && (!rbf || inl) && s.wk.SEG <= ctx->xq.cap &&
+               !g.tape && !jac && fit) {
+        step = STEP_PEER;   // the peer exchange is attached and the segments fit its slots; otherwise the RCCL / group path runs
+    } else if (one && ctx->fused && fit && rbf && steps && ctx->slot[PILCO_SLOT_POLICY].wk.PL > 0) {
+        step = STEP_FUSED_RBF;
+    }
+    r.step = H > 0 ? step : STEP_NONE;
+    r.policy = rbf ? (inl ? 1 : 2) : 0;
+    r.pair = !steps ? -1 : step == STEP_SMALL ? (jac ? 5 : 3) : jac ? 4 : ctx->variant;
+    r.timed = timed;
+    plan.route = r;
+    plan.g.pol_inline = inl ? 1 : 0;
+    auto& w = ctx->route;
+    w[ROUTE_STEP] = r.step;
+    w[ROUTE_POLICY] = r.policy;
+    w[ROUTE_DT] = mm_prep_dt(s.D);
+    w[ROUTE_KP] = s.wk.KP;
+    w[ROUTE_VSEP] = s.wk.vsep ? 1 : 0;
+    w[ROUTE_PAIR] = r.pair;
+    w[ROUTE_TAPE] = jac ? 2 : (g.tape ? 1 : 0);
+    w[ROUTE_H] = H;
+    w[ROUTE_NPAD] = s.npad;
+    return PILCO_OK;
 }
+
+// Jacobian tape: the sums, moments and records of steps [t0, t1) in two launches behind the chain (rollout_jtape enqueues
+// them per chunk of steps, last steps first, each followed by its download: the host's reverse sweep works on one chunk
+// while the device finishes the next)
 static void jac_finish_range(pilco_ctx* ctx, const RolloutPlan& plan, int t0, int t1, const RevLocalArgs* rl = nullptr) {
     Slot& s = ctx->slot[0];
     hipStream_t st = ctx->st;
@@ -277,293 +307,215 @@ static void jac_finish_range(pilco_ctx* ctx, const RolloutPlan& plan, int t0, in
     launch_mm_jac_finish(st, model_of(s), s.wk, t1 - t0, s.jac_rowmom.p + o * mm_jac_rowmom_size(s.npad, P),
                          s.jac_cpart.p + o * mm_jac_cpart_size(s.npad, P, s.wk.EL), s.jac_head.p + o * mm_jac_head_size(D, E, P),
                          s.jac_part.p + o * mm_jac_part_size(D, E, P, s.npad), plan.g.tape + o * TS, TS, plan.jrec + o * plan.jstride,
-                         plan.jsmall, rl);
-}
-int enqueue_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H, std::vector<hipEvent_t>* pair_ev) {
-    return enqueue_rollout_steps(ctx, plan, H, pair_ev);
+                         s.wk.NCH * plan.route.ncs, rl);   // (the small step's chunks per pair, or 0)
 }
 
-static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::vector<hipEvent_t>* pair_ev) {
+// The reward of a state (pilco.py:133) rides in a spare workgroup of a head or prep launch: of the state the link holds in
+// LDS, or (m_x given: the three-kernel step) of the state at m_x
+static PrepReward reward_arg(const RolloutPlan& plan, const double* m_x = nullptr) {
+    PrepReward pr{};
+    pr.n = plan.g.n_rewards;
+    pr.E = plan.E;
+    for (int i = 0; i < plan.g.n_rewards; ++i) pr.rw[i] = plan.g.rw[i];
+    if (m_x) {
+        pr.m_x = m_x;
+        pr.s_x = m_x + plan.E;
+    }
+    pr.reward = plan.g.reward;
+    return pr;
+}
+// Head of step h: its link turns state h - 1 into state h (h > 0) and hands state h on.  The state and s1 the link reads
+// (written by the launch before) and those it writes alternate between two buffers, because the workgroups of one launch
+// are not ordered.
+static GlueArgs head_args(const RolloutPlan& plan, const GlueArgs& g, int h, int flags) {
+    GlueArgs gh = g;
+    gh.step = h;
+    gh.flags = flags;
+    gh.m_x = plan.st[h > 0 ? (h - 1) & 1 : 0];
+    gh.s_x = gh.m_x + plan.E;
+    gh.m_out = h > 0 ? plan.st[h & 1] : nullptr;
+    gh.s_out = h > 0 ? plan.st[h & 1] + plan.E : nullptr;
+    gh.s1 = plan.s1b[(h + 1) & 1];
+    gh.s1_out = plan.s1b[h & 1];
+    return gh;
+}
+// The closing glue launch: state H from state H - 1
+static GlueArgs closing_args(const RolloutPlan& plan, const GlueArgs& g, int H, int flags) {
+    GlueArgs gf = g;
+    gf.step = H;
+    gf.flags = flags;
+    gf.m_x = plan.st[(H - 1) & 1];
+    gf.s_x = gf.m_x + plan.E;
+    gf.m_out = plan.st[H & 1];
+    gf.s_out = gf.m_out + plan.E;
+    gf.s1 = plan.s1b[(H - 1) & 1];
+    gf.s1_out = nullptr;
+    return gf;
+}
+// The dynamics step's O(N^2) launch of step t -- the pair kernel, or with the Jacobian tape the reverse sweep, which writes
+// the step's records -- bracketed by an event pair in a timed rollout
+static int dyn_pairs(pilco_ctx* ctx, const RolloutPlan& plan, const MMModel& md, const MMWork& w, int t) {
+    const Slot& s = ctx->slot[0];
+    if (plan.route.timed) HIPCHK(hipEventRecord(ctx->pair_events[2 * t], ctx->st));
+    if (plan.jrec)
+        launch_mm_sweep(ctx->st, md, w, s.jac_rowmom.p + (size_t)t * mm_jac_rowmom_size(s.npad, s.wk.PL),
+                        s.jac_cpart.p + (size_t)t * mm_jac_cpart_size(s.npad, s.wk.PL, s.wk.EL),
+                        s.jac_head.p + (size_t)t * mm_jac_head_size(s.D, s.E, s.wk.PL), s.jac_np.p);
+    else
+        launch_mm_pair(ctx->st, md, w, ctx->variant);
+    if (plan.route.timed) HIPCHK(hipEventRecord(ctx->pair_events[2 * t + 1], ctx->st));
+    return PILCO_OK;
+}
+
+// STEP_FUSED / STEP_SMALL: launch h = 0..H-1 is [serial link producing state h and its joint Gaussian | operands of step h],
+// followed by the pair kernel of step h; one plain glue launch closes the rollout.  What the link reads (previous step's
+// pair_isdet / mean_part / s1 / state) and what the same launch writes alternate between two buffer sets.  The one-launch
+// small step runs the pair sums (or the reverse sweep) of step h inside head h.
+static int enqueue_fused(pilco_ctx* ctx, const RolloutPlan& plan, const GlueArgs& g, int H) {
     Slot& s = ctx->slot[0];
     const MMModel md = model_of(s);
-    const int E = plan.E;
-    GlueArgs g = plan.g;
+    const bool small = plan.route.step == STEP_SMALL, jac = plan.jrec != nullptr, rew = g.n_rewards > 0 && !MM_ABL(s.wk, 8);
+    MMWork wkb[2] = {g.wk, g.wk};
+    wkb[1].pair_isdet = s.alt_isdet;
+    wkb[1].mean_part = s.alt_mean;
+    if (small)
+        for (int k = 0; k < 2; ++k) {
+            wkb[k].fuse_pair = jac ? 2 : 1;
+            wkb[k].sk_waves = 0;           // the link packs tile partials: one per (pair, row chunk)
+            wkb[k].NCS = plan.route.ncs;
+            wkb[k].share_cu = ctx->share_cu;
+            wkb[k].NT = g.wk.NCH * plan.route.ncs;
+            wkb[k].pair_part = s.w_fpart.p + (size_t)k * std::max(g.wk.PL, 1) * g.wk.NCH * 4 * 2;
+        }
+    const PrepReward pr = reward_arg(plan);   // reward of state h, from the link's LDS copy of the state
+    for (int h = 0; h < H; ++h) {
+        GlueArgs gh = head_args(plan, g, h, GF_TRAJ | GF_POLICY | (h > 0 ? (GF_PACK | GF_ASSEMBLE | GF_PROPAGATE) : 0));
+        gh.dbg_off = h > 0 ? 48 : 0;              // fused heads stamp slots 56..61 (the closing k_glue keeps 8..13)
+        gh.wk = wkb[(h + 1) & 1];                 // read side: written by launch h - 1
+        MMWork wh = wkb[h & 1];
+        if (small && jac) wh.sw_gpart = s.jac_rowmom.p + (size_t)h * mm_jac_rowmom_size(s.npad, s.wk.PL);
+        launch_mm_prep(ctx->st, md, wh, rew ? &pr : nullptr, &gh);
+        if (!small)
+            if (int r = dyn_pairs(ctx, plan, md, wkb[h & 1], h)) return r;
+    }
+    GlueArgs gf = closing_args(plan, g, H, GF_PACK | GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ);
+    gf.wk = wkb[(H - 1) & 1];
+    launch_glue(ctx->st, gf);
+    return PILCO_OK;
+}
+
+// STEP_PEER: sharded rollout with the peer exchange (GlueArgs::xq): per step
+//   head  [wait for the W flags of exchange h - 1, segments from the own area -> assemble / propagate / controller
+//          / joint, redundantly in every workgroup | operands of step h]        (ranks without pairs: a plain k_glue)
+//   pairs of this rank
+//   push  [pack this rank's segment, store it into every rank's area, raise the flag there]   (one workgroup)
+// No host involvement and no collective launch per step; the state and s1 alternate between two buffers as in the
+// single-rank fused path.  The reward of state h is taken by head h (k_glue launches: by the launch that propagates
+// state h, from its pre-propagation copy), i.e. in the same order on every rank.
+static int enqueue_peer(pilco_ctx* ctx, const RolloutPlan& plan, const GlueArgs& g, int H) {
+    Slot& s = ctx->slot[0];
+    const MMModel md = model_of(s);
     const bool rew = g.n_rewards > 0 && !MM_ABL(s.wk, 8);
-    HIPCHK(hipMemsetAsync(g.reward, 0, sizeof(double), ctx->st));
-    g.step = 0;
-    g.m_x = plan.st[0];
-    g.s_x = plan.st[0] + E;
-    g.m_out = nullptr;
-    g.s_out = nullptr;
-    const bool rbf = (g.pol_kind == PILCO_POLICY_RBF);
-    // Jacobian tape (bwd.hip): the dynamics step runs the reverse sweep in place of the forward pair kernel; the serial
-    // link packs N_ab from the per-workgroup partials the sweep leaves in the tile-partial layout
-    const bool jac = plan.jrec != nullptr;
-    auto& rt = ctx->route;   // pilco_debug_last_route: the branch taken below
-    rt[ROUTE_DT] = mm_prep_dt(s.D);
-    rt[ROUTE_KP] = s.wk.KP;
-    rt[ROUTE_VSEP] = s.wk.vsep ? 1 : 0;
-    rt[ROUTE_TAPE] = jac ? 2 : (g.tape ? 1 : 0);
-    rt[ROUTE_H] = H;
-    rt[ROUTE_NPAD] = s.npad;
-    rt[ROUTE_STEP] = 0;
-    rt[ROUTE_PAIR] = -1;
-    auto route = [&](int step, bool inline_pol, int pair) {
-        rt[ROUTE_STEP] = H > 0 ? step : 0;
-        rt[ROUTE_POLICY] = rbf ? (inline_pol ? 1 : 2) : 0;
-        rt[ROUTE_PAIR] = (s.wk.PL > 0 && H > 0) ? pair : -1;
-    };
-    const int pair_launch = jac ? 4 : ctx->variant;   // what dyn_pairs launches
-    MMWork wk0 = s.wk;
-    if (jac) {
-        wk0.sk_waves = 0;
-        wk0.NT = mm_jac_nt(s.npad, s.wk.P);
-        wk0.pair_part = s.jac_np.p;
-        g.wk = wk0;
-    }
-    const size_t j_rm = jac ? mm_jac_rowmom_size(s.npad, s.wk.PL) : 0, j_cp = jac ? mm_jac_cpart_size(s.npad, s.wk.PL, s.wk.EL) : 0,
-                 j_hd = jac ? mm_jac_head_size(s.D, s.E, s.wk.PL) : 0;
-    auto dyn_pairs = [&](const MMWork& w, int t) {
-        if (jac)
-            launch_mm_sweep(ctx->st, md, w, s.jac_rowmom.p + (size_t)t * j_rm, s.jac_cpart.p + (size_t)t * j_cp,
-                            s.jac_head.p + (size_t)t * j_hd, s.jac_np.p);
-        else
-            launch_mm_pair(ctx->st, md, w, ctx->variant);
-    };
-    bool fits = fused_heads_fit(ctx, plan);
-    // An RbfController evaluated inside the link (GlueArgs::pol_inline) makes the step the LinearController's: two launches.
-    const bool inl = rbf && g.pol_inline && ctx->fused && fits && ctx->nranks == 1 && !ctx->comm && s.wk.PL > 0 && H > 0;
-    const bool inl_peer = rbf && g.pol_inline && peer_rollout_applies(ctx, plan, H);   // sharded rollout over the peer exchange
-    // Several ranks: the policy GP is never sharded (every rank holds all of it) and its own launches would deal its pairs over
-    // the ranks, so it is evaluated INSIDE the link -- by the fused head over the peer exchange, or (value-and-gradient
-    // rollouts: the Jacobian tape runs the three-kernel step with the all-gather) by the link kernel itself.
-    const bool inl_link = rbf && g.pol_inline && !inl && !inl_peer && (ctx->nranks != 1 || ctx->comm);
-    if (rbf && (ctx->nranks != 1 || ctx->comm) && !inl_peer && !inl_link)
-        return fail(ctx, PILCO_E_STATE, "rollout: several ranks run an RbfController only with the inline policy (at most 256 basis functions, see pilco_set_inline_policy)");
-    if (rbf && !inl && !inl_peer && !inl_link && g.pol_inline) {   // not this time (three-kernel step, ...): the policy GP gets its own launches
-        g.pol_inline = 0;
-        plan.g.pol_inline = 0;
-        fits = fused_heads_fit(ctx, plan);
-    }
-    if (ctx->fused && fits && (!rbf || inl) && ctx->nranks == 1 && !ctx->comm && s.wk.PL > 0 && H > 0) {
-        // Fused head: launch h = 0..H-1 is [serial link producing state h and its joint Gaussian | operands of step h],
-        // followed by the pair kernel of step h; one plain glue launch closes the rollout.  What the link reads
-        // (previous step's pair_isdet / mean_part / s1 / state) and what the same launch writes alternate between two
-        // buffer sets, because the workgroups of one launch are not ordered.
-        MMWork wkb[2] = {wk0, wk0};
-        wkb[1].pair_isdet = s.alt_isdet;
-        wkb[1].mean_part = s.alt_mean;
-        // Small models: the pair sums ride in the head launch (prep_device.h) -- one launch per step.  The head instantiated for
-        // this input dimension carries the pair arithmetic of ONE contraction depth (that of D = DT); the workgroup's rows must
-        // be whole 32-row groups and one thread per point must cover the columns.
-        const int dtk = s.D <= 4 ? 4 : s.D <= 6 ? 6 : s.D <= 8 ? 8 : s.D <= 10 ? 10 : s.D == 11 ? 11 : s.D <= 12 ? 12 : s.D <= 14 ? 14 : s.D <= 16 ? 16 : 32;
-        // Value-and-gradient rollouts (the Jacobian tape) take the same road when the workgroup's operands stay in LDS (64-row
-        // chunks, KP <= 16; the tape serves D <= 14): the pair workgroups run the reverse sweep of their block (small_sweep).
-        const bool small_ok = ctx->fuse_small && s.npad <= 256 && (s.npad / wk0.NCH) % 32 == 0 && wk0.KP == mm_kp(dtk) &&
-                              (wk0.vsep != 0) == mm_vsep(dtk) && !pair_ev && !MM_ABL(s.wk, 255);
-        // value-and-gradient rollouts: the PLAN has decided (jac_small_chunks sized the tape and the finish for it); the step
-        // geometry seen here must agree, or the finish would read the tape in the wrong layout
-        if (jac && plan.jsmall > 0 && !small_ok) return fail(ctx, PILCO_E_STATE, "rollout: the planned one-launch small step does not fit the step's geometry");
-        const bool small = jac ? (plan.jsmall > 0) : (small_ok && ctx->variant == 0);
-        route(small ? 2 : 1, rbf, small ? (jac ? 5 : 3) : pair_launch);
-        if (small)
-            for (int k = 0; k < 2; ++k) {
-                wkb[k].fuse_pair = jac ? 2 : 1;
-                wkb[k].sk_waves = 0;           // the link packs tile partials: one per (pair, row chunk)
-                wkb[k].NCS = small_col_splits(ctx, s, rew);
-                wkb[k].share_cu = ctx->share_cu;
-                wkb[k].NT = wk0.NCH * wkb[k].NCS;
-                wkb[k].pair_part = s.w_fpart.p + (size_t)k * std::max(wk0.PL, 1) * wk0.NCH * 4 * 2;
-            }
-        size_t evi = 0;
-        for (int h = 0; h < H; ++h) {
-            GlueArgs gh = g;
-            gh.step = h;
-            gh.dbg_off = h > 0 ? 48 : 0;              // fused heads stamp slots 56..61 (the closing k_glue keeps 8..13)
-            gh.wk = wkb[(h + 1) & 1];                 // read side: written by launch h - 1
-            gh.flags = GF_TRAJ | GF_POLICY | (h > 0 ? (GF_PACK | GF_ASSEMBLE | GF_PROPAGATE) : 0);
-            gh.m_x = plan.st[h > 0 ? (h - 1) & 1 : 0];
-            gh.s_x = gh.m_x + E;
-            gh.m_out = h > 0 ? plan.st[h & 1] : nullptr;
-            gh.s_out = h > 0 ? plan.st[h & 1] + E : nullptr;
-            gh.s1 = plan.s1b[(h + 1) & 1];
-            gh.s1_out = plan.s1b[h & 1];
-            PrepReward pr{};
-            if (rew) {   // reward of state h (pilco.py:133), from the link's LDS copy of the state
-                pr.n = g.n_rewards;
-                pr.E = E;
-                for (int i = 0; i < g.n_rewards; ++i) pr.rw[i] = g.rw[i];
-                pr.reward = g.reward;
-            }
-            if (small && jac) {
-                MMWork wh = wkb[h & 1];
-                wh.sw_gpart = s.jac_rowmom.p + (size_t)h * j_rm;
-                launch_mm_prep(ctx->st, md, wh, rew ? &pr : nullptr, &gh);
-                continue;
-            }
-            launch_mm_prep(ctx->st, md, wkb[h & 1], rew ? &pr : nullptr, &gh);
-            if (small) continue;
-            if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
-            dyn_pairs(wkb[h & 1], h);
-            if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
+    PeerXch& x = ctx->xq;
+    {   // executed now (not being captured into a graph): this rollout's epoch base goes up ahead of its launches
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIPCHK(hipStreamIsCapturing(ctx->st, &cs));
+        if (cs == hipStreamCaptureStatusNone) {
+            if (int r = xq_begin(ctx)) return r;
+            x.epoch += (unsigned long long)H;
         }
-        GlueArgs gf = g;
-        gf.step = H;
-        gf.wk = wkb[(H - 1) & 1];
-        gf.flags = GF_PACK | GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ;
-        gf.m_x = plan.st[(H - 1) & 1];
-        gf.s_x = gf.m_x + E;
-        gf.m_out = plan.st[H & 1];
-        gf.s_out = gf.m_out + E;
-        gf.s1 = plan.s1b[(H - 1) & 1];
-        gf.s1_out = nullptr;
-        launch_glue(ctx->st, gf);
-        return PILCO_OK;
     }
+    const int spin = 2000000;   // ~2 s of polling before a wait gives up
+    // Contexts of ONE process sharing a GPU (pilco_rollout_group after pilco_group_peer_attach): their streams may share
+    // hardware queues, which start their packets in order, so a rank's flag wait could sit in a queue ahead of the push
+    // it waits for.  The ranks' host threads therefore enqueue in lockstep -- every rank's push of step h is in the
+    // queues before any rank's wait for it -- and run_rollout does not capture these rollouts into a graph.
+    PeerGroup* lockstep = (x.wait_kernel && ctx->group) ? ctx->group.get() : nullptr;
+    auto with_xq = [&](GlueArgs& ga, int k) {
+        ga.xq = x.local;
+        ga.xq_k = k;
+        ga.xq_W = x.W;
+        ga.xq_cap = x.cap;
+        ga.xq_spin = x.wait_kernel ? 1000 : spin;   // behind a wait launch the flags are already up
+    };
+    const PrepReward pr = reward_arg(plan);
+    for (int h = 0; h < H; ++h) {
+        GlueArgs gh = head_args(plan, g, h, GF_TRAJ | GF_POLICY | (h > 0 ? (GF_ASSEMBLE | GF_PROPAGATE) : 0));
+        gh.wk = s.wk;
+        if (h > 0) {
+            with_xq(gh, h - 1);
+            if (x.wait_kernel) launch_peer_wait(ctx->st, x.local, h - 1, x.W, spin);
+        }
+        if (s.wk.PL > 0) {
+            launch_mm_prep(ctx->st, md, s.wk, rew ? &pr : nullptr, &gh);
+            if (int r = dyn_pairs(ctx, plan, md, s.wk, h)) return r;
+        } else {
+            launch_glue(ctx->st, gh, rew && h > 0);   // its reward workgroup takes the pre-propagation state h - 1
+        }
+        GlueArgs gp = g;
+        gp.step = h + 1;
+        gp.wk = s.wk;
+        gp.flags = GF_PACK;
+        with_xq(gp, h);
+        gp.xq_peers = x.d_peers;
+        launch_glue(ctx->st, gp);
+        if (lockstep && !lockstep->arrive_and_wait()) return fail(ctx, PILCO_E_STATE, "rollout: another rank of the group failed");
+    }
+    GlueArgs gf = closing_args(plan, g, H, GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ);
+    gf.wk = s.wk;
+    with_xq(gf, H - 1);
+    if (x.wait_kernel) launch_peer_wait(ctx->st, x.local, H - 1, x.W, spin);
+    launch_glue(ctx->st, gf, rew && s.wk.PL == 0);
+    return PILCO_OK;
+}
+
+// STEP_FUSED_RBF: fused heads with an RbfController (controllers.py:108-121): the policy is a moment-matching GP of its own,
+// so a step is two head + pair rounds and the serial link splits in two:
+//   policy head   [pack / assemble / propagate of step h - 1 -> state h | operands of the POLICY GP at state h]
+//   policy pairs
+//   dynamics head [reduce the policy GP, S -= diag(var - 1e-6), squash, joint Gaussian | operands of step h]
+//   dynamics pairs
+// four launches per step instead of six (two of them single-workgroup glue launches).  What a head's link reads was
+// written by EARLIER launches and what its prep part writes belongs to the other GP: no double buffering beyond the
+// state's (one s1).
+static int enqueue_fused_rbf(pilco_ctx* ctx, const RolloutPlan& plan, const GlueArgs& g, int H) {
+    Slot& s = ctx->slot[0];
     Slot& ps = ctx->slot[PILCO_SLOT_POLICY];
-    const MMModel pmd = rbf ? model_of(ps) : MMModel{};
-    if (peer_rollout_applies(ctx, plan, H)) {
-        // Sharded rollout with the peer exchange (GlueArgs::xq): per step
-        //   head  [wait for the W flags of exchange h - 1, segments from the own area -> assemble / propagate / controller
-        //          / joint, redundantly in every workgroup | operands of step h]        (ranks without pairs: a plain k_glue)
-        //   pairs of this rank
-        //   push  [pack this rank's segment, store it into every rank's area, raise the flag there]   (one workgroup)
-        // No host involvement and no collective launch per step; the state and s1 alternate between two buffers as in the
-        // single-rank fused path.  The reward of state h is taken by head h (k_glue launches: by the launch that
-        // propagates state h, from its pre-propagation copy), i.e. in the same order on every rank.
-        route(5, rbf, s.wk.PL > 0 ? ctx->variant : -1);
-        PeerXch& x = ctx->xq;
-        {   // executed now (not being captured into a graph): this rollout's epoch base goes up ahead of its launches
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            HIPCHK(hipStreamIsCapturing(ctx->st, &cs));
-            if (cs == hipStreamCaptureStatusNone) {
-                if (int r = xq_begin(ctx)) return r;
-                x.epoch += (unsigned long long)H;
-            }
-        }
-        const int spin = 2000000;   // ~2 s of polling before a wait gives up
-        // Contexts of ONE process sharing a GPU (pilco_rollout_group after pilco_group_peer_attach): their streams may share
-        // hardware queues, which start their packets in order, so a rank's flag wait could sit in a queue ahead of the push
-        // it waits for.  The ranks' host threads therefore enqueue in lockstep -- every rank's push of step h is in the
-        // queues before any rank's wait for it -- and run_rollout does not capture these rollouts into a graph.
-        PeerGroup* lockstep = (x.wait_kernel && ctx->group) ? ctx->group.get() : nullptr;
-        auto with_xq = [&](GlueArgs& ga, int k) {
-            ga.xq = x.local;
-            ga.xq_k = k;
-            ga.xq_W = x.W;
-            ga.xq_cap = x.cap;
-            ga.xq_spin = x.wait_kernel ? 1000 : spin;   // behind a wait launch the flags are already up
-        };
-        PrepReward pr{};
-        if (rew) {
-            pr.n = g.n_rewards;
-            pr.E = E;
-            for (int i = 0; i < g.n_rewards; ++i) pr.rw[i] = g.rw[i];
-            pr.reward = g.reward;
-        }
-        size_t evi = 0;
-        for (int h = 0; h < H; ++h) {
-            GlueArgs gh = g;
-            gh.step = h;
-            gh.wk = s.wk;
-            gh.flags = GF_TRAJ | GF_POLICY | (h > 0 ? (GF_ASSEMBLE | GF_PROPAGATE) : 0);
-            gh.m_x = plan.st[h > 0 ? (h - 1) & 1 : 0];
-            gh.s_x = gh.m_x + E;
-            gh.m_out = h > 0 ? plan.st[h & 1] : nullptr;
-            gh.s_out = h > 0 ? plan.st[h & 1] + E : nullptr;
-            gh.s1 = plan.s1b[(h + 1) & 1];
-            gh.s1_out = plan.s1b[h & 1];
-            if (h > 0) {
-                with_xq(gh, h - 1);
-                if (x.wait_kernel) launch_peer_wait(ctx->st, x.local, h - 1, x.W, spin);
-            }
-            if (s.wk.PL > 0) {
-                launch_mm_prep(ctx->st, md, s.wk, rew ? &pr : nullptr, &gh);
-                if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
-                launch_mm_pair(ctx->st, md, s.wk, ctx->variant);
-                if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
-            } else {
-                launch_glue(ctx->st, gh, rew && h > 0);   // its reward workgroup takes the pre-propagation state h - 1
-            }
-            GlueArgs gp = g;
-            gp.step = h + 1;
-            gp.wk = s.wk;
-            gp.flags = GF_PACK;
-            with_xq(gp, h);
-            gp.xq_peers = x.d_peers;
-            launch_glue(ctx->st, gp);
-            if (lockstep && !lockstep->arrive_and_wait()) return fail(ctx, PILCO_E_STATE, "rollout: another rank of the group failed");
-        }
-        GlueArgs gf = g;
-        gf.step = H;
-        gf.wk = s.wk;
-        gf.flags = GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ;
-        gf.m_x = plan.st[(H - 1) & 1];
-        gf.s_x = gf.m_x + E;
-        gf.m_out = plan.st[H & 1];
-        gf.s_out = gf.m_out + E;
-        gf.s1 = plan.s1b[(H - 1) & 1];
-        gf.s1_out = nullptr;
-        with_xq(gf, H - 1);
-        if (x.wait_kernel) launch_peer_wait(ctx->st, x.local, H - 1, x.W, spin);
-        launch_glue(ctx->st, gf, rew && s.wk.PL == 0);
-        return PILCO_OK;
+    const MMModel md = model_of(s), pmd = model_of(ps);
+    const bool rew = g.n_rewards > 0 && !MM_ABL(s.wk, 8);
+    const PrepReward pr = reward_arg(plan);   // reward of state h, from the link's LDS copy of the state
+    for (int h = 0; h < H; ++h) {
+        GlueArgs ga = head_args(plan, g, h, GF_TRAJ | GF_RBF_PRE | (h > 0 ? (GF_PACK | GF_ASSEMBLE | GF_PROPAGATE) : 0));
+        ga.dbg_off = h > 0 ? 48 : 0;
+        ga.s1 = g.s1;
+        ga.s1_out = g.s1_out;
+        launch_mm_prep(ctx->st, pmd, ps.wk, rew ? &pr : nullptr, &ga);
+        launch_mm_pair(ctx->st, pmd, ps.wk, ctx->variant);
+        GlueArgs gc = g;
+        gc.step = h;
+        gc.flags = GF_RBF_POST | GF_POLICY;
+        gc.m_x = plan.st[h & 1];
+        gc.s_x = gc.m_x + plan.E;
+        gc.m_out = nullptr;
+        gc.s_out = nullptr;
+        launch_mm_prep(ctx->st, md, s.wk, nullptr, &gc);
+        if (int r = dyn_pairs(ctx, plan, md, s.wk, h)) return r;
     }
-    if (ctx->fused && fits && rbf && ctx->nranks == 1 && !ctx->comm && s.wk.PL > 0 && ps.wk.PL > 0 && H > 0) {
-        // Fused heads with an RbfController (controllers.py:108-121): the policy is a moment-matching GP of its own, so a
-        // step is two head + pair rounds and the serial link splits in two:
-        //   policy head   [pack / assemble / propagate of step h - 1 -> state h | operands of the POLICY GP at state h]
-        //   policy pairs
-        //   dynamics head [reduce the policy GP, S -= diag(var - 1e-6), squash, joint Gaussian | operands of step h]
-        //   dynamics pairs
-        // four launches per step instead of six (two of them single-workgroup glue launches).  What a head's link reads
-        // was written by EARLIER launches and what its prep part writes belongs to the other GP: no double buffering
-        // beyond the state's.
-        route(4, false, pair_launch);
-        size_t evi = 0;
-        for (int h = 0; h < H; ++h) {
-            GlueArgs ga = g;
-            ga.step = h;
-            ga.dbg_off = h > 0 ? 48 : 0;
-            ga.flags = GF_TRAJ | GF_RBF_PRE | (h > 0 ? (GF_PACK | GF_ASSEMBLE | GF_PROPAGATE) : 0);
-            ga.m_x = plan.st[h > 0 ? (h - 1) & 1 : 0];
-            ga.s_x = ga.m_x + E;
-            ga.m_out = h > 0 ? plan.st[h & 1] : nullptr;
-            ga.s_out = h > 0 ? plan.st[h & 1] + E : nullptr;
-            PrepReward pr{};
-            if (rew) {   // reward of state h (pilco.py:133), from the link's LDS copy of the state
-                pr.n = g.n_rewards;
-                pr.E = E;
-                for (int i = 0; i < g.n_rewards; ++i) pr.rw[i] = g.rw[i];
-                pr.reward = g.reward;
-            }
-            launch_mm_prep(ctx->st, pmd, ps.wk, rew ? &pr : nullptr, &ga);
-            launch_mm_pair(ctx->st, pmd, ps.wk, ctx->variant);
-            GlueArgs gc = g;
-            gc.step = h;
-            gc.flags = GF_RBF_POST | GF_POLICY;
-            gc.m_x = plan.st[h & 1];
-            gc.s_x = gc.m_x + E;
-            gc.m_out = nullptr;
-            gc.s_out = nullptr;
-            launch_mm_prep(ctx->st, md, s.wk, nullptr, &gc);
-            if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
-            dyn_pairs(s.wk, h);
-            if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
-        }
-        GlueArgs gf = g;
-        gf.step = H;
-        gf.flags = GF_PACK | GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ;
-        gf.m_x = plan.st[(H - 1) & 1];
-        gf.s_x = gf.m_x + E;
-        gf.m_out = plan.st[H & 1];
-        gf.s_out = gf.m_out + E;
-        launch_glue(ctx->st, gf);
-        return PILCO_OK;
-    }
-    // RBF policy (controllers.py:108-121): the glue that produced the state hands it to the policy GP
-    // (GF_RBF_PRE), the policy's moment matching runs as its own prep/pair, a second glue squashes and
-    // builds the joint Gaussian (GF_RBF_POST | GF_POLICY).
+    GlueArgs gf = closing_args(plan, g, H, GF_PACK | GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ);
+    gf.s1 = g.s1;
+    launch_glue(ctx->st, gf);
+    return PILCO_OK;
+}
+
+// STEP_THREE: per step a prep launch, the pair launch and a glue launch (pack / assemble / propagate / policy; several
+// ranks: a pack launch and the all-gather of the segments in between).  An RbfController with launches of its own
+// (controllers.py:108-121): the glue that produced the state hands it to the policy GP (GF_RBF_PRE), the policy's moment
+// matching runs as its own prep/pair, a second glue squashes and builds the joint Gaussian (GF_RBF_POST | GF_POLICY).
+static int enqueue_three_kernel(pilco_ctx* ctx, const RolloutPlan& plan, GlueArgs g, int H) {
+    Slot& s = ctx->slot[0];
+    Slot& ps = ctx->slot[PILCO_SLOT_POLICY];
+    const bool rbf = g.pol_kind == PILCO_POLICY_RBF, rew = g.n_rewards > 0 && !MM_ABL(s.wk, 8);
+    const MMModel md = model_of(s), pmd = rbf ? model_of(ps) : MMModel{};
     auto policy_stage = [&](GlueArgs& ga) {
         launch_mm_prep(ctx->st, pmd, ps.wk);
         launch_mm_pair(ctx->st, pmd, ps.wk, ctx->variant);
@@ -572,34 +524,22 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
         launch_glue(ctx->st, ga);
         ga.flags = keep;
     };
-    const bool rbf_l = rbf && !inl_link;   // the policy GP as launches of its own (an inline policy is part of the link kernel)
-    route(3, !rbf_l, pair_launch);
+    const bool rbf_l = rbf && !g.pol_inline;   // the policy GP as launches of its own (an inline policy is part of the link kernel)
     g.flags = GF_TRAJ | (H > 0 ? (rbf_l ? GF_RBF_PRE : GF_POLICY) : 0);
     launch_glue(ctx->st, g);
     if (rbf_l && H > 0) policy_stage(g);
-    size_t evi = 0;
     for (int t = 0; t < H; ++t) {
         if (s.wk.PL > 0) {
-            PrepReward pr{};
-            if (rew) {   // reward of state t rides in a spare workgroup of this step's prep launch
-                pr.n = g.n_rewards;
-                pr.E = E;
-                for (int i = 0; i < g.n_rewards; ++i) pr.rw[i] = g.rw[i];
-                pr.m_x = plan.st[t & 1];
-                pr.s_x = plan.st[t & 1] + E;
-                pr.reward = g.reward;
-            }
+            const PrepReward pr = reward_arg(plan, plan.st[t & 1]);   // reward of state t
             launch_mm_prep(ctx->st, md, s.wk, rew ? &pr : nullptr);
             if (ctx->dbg && MM_ABL(s.wk, 64)) launch_stamp(ctx->st, ctx->dbg, 30);
-            if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
-            dyn_pairs(s.wk, t);
-            if (pair_ev) HIPCHK(hipEventRecord((*pair_ev)[evi++], ctx->st));
+            if (int r = dyn_pairs(ctx, plan, md, s.wk, t)) return r;
         }
         g.step = t + 1;
         g.m_x = plan.st[t & 1];
-        g.s_x = plan.st[t & 1] + E;
+        g.s_x = plan.st[t & 1] + plan.E;
         g.m_out = plan.st[(t + 1) & 1];
-        g.s_out = plan.st[(t + 1) & 1] + E;
+        g.s_out = plan.st[(t + 1) & 1] + plan.E;
         const bool more = t + 1 < H;
         const int tail = GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ | (more ? (rbf_l ? GF_RBF_PRE : GF_POLICY) : 0);
         if (ctx->nranks == 1 && !ctx->comm) {
@@ -620,35 +560,66 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, RolloutPlan& plan, int H, std::
     return PILCO_OK;
 }
 
-// Run one rollout: replay the cached hipGraph when the launch sequence is unchanged
-// (same buffers, sizes, horizon, policy / reward structure), otherwise (re)capture it.
-int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
+// Enqueue one full rollout of H steps along plan.route (initial state already in plan.st[0]); the final state ends up in
+// plan.st[H & 1].
+static int enqueue_rollout_steps(pilco_ctx* ctx, const RolloutPlan& plan, int H) {
     Slot& s = ctx->slot[0];
-    // With a communicator the captured graph contains the ncclAllGather nodes (RCCL supports stream
-    // capture); if capture or instantiation fails the rollout falls back to eager launches for good.
-    const bool peer = peer_rollout_applies(ctx, plan, H);   // no collective nodes: captured like a single-rank rollout
+    while (plan.route.timed && ctx->pair_events.size() < (size_t)2 * std::max(H, 1)) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        ctx->pair_events.push_back(e);
+    }
+    HIPCHK(hipMemsetAsync(plan.g.reward, 0, sizeof(double), ctx->st));
+    GlueArgs g = plan.g;
+    g.step = 0;
+    g.m_x = plan.st[0];
+    g.s_x = plan.st[0] + plan.E;
+    g.m_out = nullptr;
+    g.s_out = nullptr;
+    if (plan.jrec) {   // Jacobian tape (bwd.hip): the serial link packs N_ab from the per-workgroup partials the reverse sweep
+        g.wk.sk_waves = 0;   // leaves in the tile-partial layout
+        g.wk.NT = mm_jac_nt(s.npad, s.wk.P);
+        g.wk.pair_part = s.jac_np.p;
+    }
+    switch (plan.route.step) {
+        case STEP_FUSED:
+        case STEP_SMALL: return enqueue_fused(ctx, plan, g, H);
+        case STEP_PEER: return enqueue_peer(ctx, plan, g, H);
+        case STEP_FUSED_RBF: return enqueue_fused_rbf(ctx, plan, g, H);
+        default: return enqueue_three_kernel(ctx, plan, g, H);
+    }
+}
+
+// Run one rollout to completion: replay the cached hipGraph when the launch sequence is unchanged (same route, buffers,
+// sizes, horizon, policy / reward structure), otherwise (re)capture it first.  `upload` enqueues the initial state into
+// plan.st[0]; a capture's eager warm-up overwrites it, so it is enqueued again in front of the replay.
+template <class Upload>
+static int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H, Upload&& upload) {
+    Slot& s = ctx->slot[0];
+    if (int r = plan_route(ctx, plan, H, ctx->time_pairs)) return r;
+    const StepRoute& rt = plan.route;
+    const bool peer = rt.step == STEP_PEER;   // no collective nodes: captured like a single-rank rollout
+    // With a communicator the captured graph contains the ncclAllGather nodes (RCCL supports stream capture); if capture or
+    // instantiation fails the rollout falls back to eager launches for good.
     const bool sharded = (ctx->nranks != 1 || ctx->comm) && !peer;
+    auto eager = [&] {
+        if (int r = upload()) return r;
+        return enqueue_rollout_steps(ctx, plan, H);
+    };
     if (ctx->time_pairs) {   // measurement mode (pilco_set_pair_timing): eager, an event pair around every O(N^2) launch
-        while (ctx->pair_events.size() < (size_t)2 * std::max(H, 1)) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            ctx->pair_events.push_back(e);
-        }
         ctx->timed_pairs = 0;
-        if (int r = enqueue_rollout(ctx, plan, H, &ctx->pair_events)) return r;
+        if (int r = eager()) return r;
         ctx->timed_pairs = (s.wk.PL > 0) ? H : 0;
         return PILCO_OK;
     }
-    const bool lockstep = peer && ctx->group && ctx->xq.wait_kernel;   // enqueued step by step with the group (enqueue_rollout_steps)
+    const bool lockstep = peer && ctx->group && ctx->xq.wait_kernel;   // enqueued step by step with the group (enqueue_peer)
     if (!ctx->use_graph || lockstep || (sharded && (!ctx->comm || ctx->graph_rccl_failed)) || (ctx->dbg && !getenv("PILCO_DBG_GRAPH")))
-        return enqueue_rollout(ctx, plan, H, nullptr);
+        return eager();
     const GlueArgs& g = plan.g;
-    // (everything in the key is fixed before the launches are enqueued: enqueue_rollout_steps may clear plan.g.pol_inline when
-    // the step cannot take the inline policy, so the key holds the setting and the policy's eligibility, not that decision --
-    // a key that changed between the capture and the replay captured again and handed out the warm-up's one-step result)
     std::vector<unsigned long long> key = {
         (unsigned long long)H, (unsigned long long)g.pol_kind, (unsigned long long)g.n_rewards, (unsigned long long)g.squash,
-        (unsigned long long)ctx->variant, (unsigned long long)ctx->fused + 2ull * (unsigned long long)ctx->fuse_small + 4ull * (unsigned long long)(ctx->share_cu != 0), (unsigned long long)(uintptr_t)plan.st[0], (unsigned long long)(uintptr_t)g.s1,
+        (unsigned long long)ctx->variant, (unsigned long long)rt.step, (unsigned long long)rt.policy, (unsigned long long)(long long)rt.pair,
+        (unsigned long long)rt.ncs, (unsigned long long)(ctx->share_cu != 0), (unsigned long long)(uintptr_t)plan.st[0], (unsigned long long)(uintptr_t)g.s1,
         (unsigned long long)(uintptr_t)g.traj, (unsigned long long)(uintptr_t)g.tape, (unsigned long long)(uintptr_t)g.W, (unsigned long long)(uintptr_t)g.maxact,
         (unsigned long long)(uintptr_t)s.w_part.p, (unsigned long long)(uintptr_t)s.w_At.p, (unsigned long long)(uintptr_t)s.w_Wt.p,
         (unsigned long long)(uintptr_t)s.w_small.p, (unsigned long long)(uintptr_t)s.w_gath.p, (unsigned long long)(uintptr_t)s.w_out.p,
@@ -661,8 +632,8 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
         (unsigned long long)ctx->slot[1].n,
         (unsigned long long)ctx->slot[1].wk.sk_waves, (unsigned long long)(uintptr_t)ctx->slot[1].w_small.p,
         (unsigned long long)(uintptr_t)ctx->slot[1].w_in.p, (unsigned long long)(uintptr_t)ctx->slot[1].ls.p,
-        (unsigned long long)(peer ? 1 : 0), (unsigned long long)(uintptr_t)ctx->xq.local, (unsigned long long)ctx->nranks, (unsigned long long)ctx->rank,
-        (unsigned long long)(ctx->inline_policy && g.pol_lds > 0 ? 1 : 0), (unsigned long long)(uintptr_t)ctx->slot[1].var.p,
+        (unsigned long long)(uintptr_t)ctx->xq.local, (unsigned long long)ctx->nranks, (unsigned long long)ctx->rank,
+        (unsigned long long)(uintptr_t)ctx->slot[1].var.p,
         (unsigned long long)(uintptr_t)plan.jrec, (unsigned long long)plan.jstride, (unsigned long long)(uintptr_t)s.jac_rowmom.p,
         (unsigned long long)(uintptr_t)s.jac_cpart.p, (unsigned long long)(uintptr_t)s.jac_part.p, (unsigned long long)(uintptr_t)s.jac_head.p,
         (unsigned long long)(uintptr_t)s.jac_np.p};
@@ -682,21 +653,9 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
         key.push_back(cbits);
     }
     // a few instantiated graphs are kept (value rollouts and tape rollouts of an optimiser alternate): find this key
-    for (size_t i = 0; i < ctx->graph_cache.size(); ++i)
-        if (ctx->graph_cache[i].first == key) {
-            if (i != 0) std::swap(ctx->graph_cache[i], ctx->graph_cache[0]);   // most recently used first
-            ctx->graph = ctx->graph_cache[0].second;
-            ctx->graph_key = key;
-            const auto rk = ctx->route_of_graph.find(key);
-            for (int w = ROUTE_STEP_FIRST; w <= ROUTE_STEP_LAST; ++w) ctx->route[w] = rk != ctx->route_of_graph.end() ? rk->second[w] : -1;
-            if (peer) {
-                if (int r = xq_begin(ctx)) return r;
-                ctx->xq.epoch += (unsigned long long)H;
-            }
-            HIPCHK(hipGraphLaunch(ctx->graph, ctx->st));
-            return PILCO_OK;
-        }
-    {
+    size_t i = 0;
+    while (i < ctx->graph_cache.size() && ctx->graph_cache[i].first != key) ++i;
+    if (i == ctx->graph_cache.size()) {
         ctx->graph = nullptr;
         if (ctx->graph_cache.size() >= 4) {   // evict the least recently used
             (void)hipGraphExecDestroy(ctx->graph_cache.back().second);
@@ -704,53 +663,44 @@ int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H) {
         }
         // warm the per-kernel one-time host configuration outside the capture (a one-step rollout: with the peer
         // exchange attached every rank runs it, so it is a complete exchange of its own epoch)
-        if (int r = enqueue_rollout(ctx, plan, H > 0 ? 1 : 0, nullptr)) return r;
+        if (int r = upload()) return r;
+        if (int r = enqueue_rollout_steps(ctx, plan, H > 0 ? 1 : 0)) return r;
         HIPCHK(hipStreamSynchronize(ctx->st));
         hipGraph_t graph = nullptr;
         HIPCHK(hipStreamBeginCapture(ctx->st, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_rollout(ctx, plan, H, nullptr);
+        const int rc = enqueue_rollout_steps(ctx, plan, H);
         hipError_t e = hipStreamEndCapture(ctx->st, &graph);
+        auto eager_for_good = [&] {   // a sharded capture that fails is not fatal: this and all later sharded rollouts run eagerly
+            ctx->graph_rccl_failed = true;
+            (void)hipGetLastError();
+            return eager();
+        };
         if (rc != PILCO_OK) {
             if (graph) (void)hipGraphDestroy(graph);
-            if (sharded) {
-                ctx->graph_rccl_failed = true;
-                (void)hipGetLastError();
-                return -1;
-            }
-            return rc;
+            return sharded ? eager_for_good() : rc;
         }
-        if (e != hipSuccess) {
-            if (sharded) {  // not fatal: run this and all later sharded rollouts eagerly
-                ctx->graph_rccl_failed = true;
-                (void)hipGetLastError();
-                return -1;
-            }
-            return fail(ctx, PILCO_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        }
+        if (e != hipSuccess)
+            return sharded ? eager_for_good() : fail(ctx, PILCO_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
         e = hipGraphInstantiate(&ctx->graph, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) {
             ctx->graph = nullptr;
-            if (sharded) {
-                ctx->graph_rccl_failed = true;
-                (void)hipGetLastError();
-                return -1;
-            }
-            return fail(ctx, PILCO_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+            return sharded ? eager_for_good() : fail(ctx, PILCO_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
         }
-        ctx->graph_key = key;
         ctx->graph_cache.insert(ctx->graph_cache.begin(), std::make_pair(key, ctx->graph));
-        if (ctx->route_of_graph.size() >= 64) ctx->route_of_graph.clear();   // (keys of evicted graphs; bounded)
-        ctx->route_of_graph[key] = ctx->route;
-        // the warm-up rollout above overwrote the initial state: the caller re-uploads it (see callers)
-        return -1;
+    } else if (i != 0) {
+        std::swap(ctx->graph_cache[i], ctx->graph_cache[0]);   // most recently used first
     }
+    ctx->graph = ctx->graph_cache[0].second;
+    ctx->graph_key = key;
+    if (int r = upload()) return r;
+    if (peer) {
+        if (int r = xq_begin(ctx)) return r;
+        ctx->xq.epoch += (unsigned long long)H;
+    }
+    HIPCHK(hipGraphLaunch(ctx->graph, ctx->st));
+    return PILCO_OK;
 }
-
-
-extern "C" {
-
-}  // extern "C"
 
 // pilco_rollout in two halves, so that several rollouts (the lanes of pilco_rollout_batch) can be in flight at once:
 // rollout_begin enqueues everything -- upload of (m0, S0), the rollout, the downloads into pinned memory -- and returns;
@@ -781,20 +731,16 @@ static int rollout_begin(pilco_ctx* ctx, const pilco_policy* policy, const pilco
     double* pin_out = ctx->pin_io + nst;
     memcpy(pin_in, m0, sizeof(double) * E);
     memcpy(pin_in + E, S0, sizeof(double) * E * E);
-    int rr = -1;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    auto upload = [&]() -> int {
         HIPCHK(hipMemcpyAsync(plan.st[0], pin_in, sizeof(double) * nst, hipMemcpyHostToDevice, ctx->st));
-        rr = run_rollout(ctx, plan, H);
-        if (rr == -1) continue;  // graph was just (re)captured: upload the state again and replay it
-        if (rr != PILCO_OK) return rr;
-        break;
-    }
-    if (rr == -1) return fail(ctx, PILCO_E_STATE, "rollout: the launch sequence was captured twice and never ran");
+        return PILCO_OK;
+    };
+    if (int r = run_rollout(ctx, plan, H, upload)) return r;
     HIPCHK(hipMemcpyAsync(pin_out, plan.st[H & 1], sizeof(double) * nst, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(pin_out + nst, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
     if (traj)
         HIPCHK(hipMemcpyAsync(traj, ctx->traj.p, sizeof(double) * (size_t)(H + 1) * (E + E * E), hipMemcpyDeviceToHost, ctx->st));
-    rc.peer = peer_rollout_applies(ctx, plan, H);
+    rc.peer = plan.route.step == STEP_PEER;
     if (rc.peer) HIPCHK(hipMemcpyAsync(ctx->xq.pin + 128, ctx->xq.local + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->st));
     rc.nst = nst;
     rc.pin_out = pin_out;
@@ -1056,35 +1002,23 @@ int pilco_rollout_timed(pilco_ctx* ctx, const pilco_policy* policy, const pilco_
     HIPCHK(hipMemcpyAsync(init, m0, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemcpyAsync(init + E, S0, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
-    {   // make sure the graph exists before the timed region
+    auto upload = [&]() -> int {
         HIPCHK(hipMemcpyAsync(plan.st[0], init, sizeof(double) * (E + E * E), hipMemcpyDeviceToDevice, ctx->st));
-        const int r = run_rollout(ctx, plan, H);
-        if (r != PILCO_OK && r != -1) return r;
-        HIPCHK(hipStreamSynchronize(ctx->st));
-    }
+        return PILCO_OK;
+    };
+    if (int r = run_rollout(ctx, plan, H, upload)) return r;   // the graph exists before the timed region
+    HIPCHK(hipStreamSynchronize(ctx->st));
     HIPCHK(hipEventRecord(ctx->ev0, ctx->st));
-    for (int rep = 0; rep < reps; ++rep) {
-        HIPCHK(hipMemcpyAsync(plan.st[0], init, sizeof(double) * (E + E * E), hipMemcpyDeviceToDevice, ctx->st));
-        int r = run_rollout(ctx, plan, H);
-        if (r == -1) {  // only possible when the sharded capture fell back to eager mode: redo this rollout
-            HIPCHK(hipMemcpyAsync(plan.st[0], init, sizeof(double) * (E + E * E), hipMemcpyDeviceToDevice, ctx->st));
-            r = run_rollout(ctx, plan, H);
-        }
-        if (r != PILCO_OK) return r;
-    }
+    for (int rep = 0; rep < reps; ++rep)
+        if (int r = run_rollout(ctx, plan, H, upload)) return r;
     HIPCHK(hipEventRecord(ctx->ev1, ctx->st));
     HIPCHK(hipEventSynchronize(ctx->ev1));
     HIPCHK(hipEventElapsedTime(ms_total, ctx->ev0, ctx->ev1));
     if (ms_pair) {
         // second pass with an event pair around every pair-kernel launch (perturbs the total, so timed separately)
-        const size_t need = (size_t)2 * H;
-        while (ctx->pair_events.size() < need) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            ctx->pair_events.push_back(e);
-        }
-        HIPCHK(hipMemcpyAsync(plan.st[0], init, sizeof(double) * (E + E * E), hipMemcpyDeviceToDevice, ctx->st));
-        if (int r = enqueue_rollout(ctx, plan, H, &ctx->pair_events)) return r;
+        if (int r = upload()) return r;
+        if (int r = plan_route(ctx, plan, H, true)) return r;
+        if (int r = enqueue_rollout_steps(ctx, plan, H)) return r;
         HIPCHK(hipStreamSynchronize(ctx->st));
         float tot = 0.f;
         int cnt = 0;
@@ -1121,16 +1055,12 @@ int pilco_rollout_tape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_r
     const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
     ENSURE(ctx->tape, std::max<size_t>(1, (size_t)H * TS));
     plan.g.tape = ctx->tape.p;
-    int rr = -1;
-    for (int attempt = 0; attempt < 2; ++attempt) {   // replayed as a hipGraph like pilco_rollout (the tape pointer is part of the graph key)
+    auto upload = [&]() -> int {
         HIPCHK(hipMemcpyAsync(plan.st[0], m0, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
         HIPCHK(hipMemcpyAsync(plan.st[0] + E, S0, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
-        rr = run_rollout(ctx, plan, H);
-        if (rr == -1) continue;
-        if (rr != PILCO_OK) return rr;
-        break;
-    }
-    if (rr == -1) return fail(ctx, PILCO_E_STATE, "rollout: the launch sequence was captured twice and never ran");
+        return PILCO_OK;
+    };
+    if (int r = run_rollout(ctx, plan, H, upload)) return r;   // replayed as a hipGraph like pilco_rollout (the tape pointer is part of the graph key)
     HIPCHK(hipMemcpyAsync(mH, plan.st[H & 1], sizeof(double) * E, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(SH, plan.st[H & 1] + E, sizeof(double) * E * E, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(reward, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
@@ -1213,19 +1143,14 @@ int rollout_jtape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward
     const bool jdirect = !dev && !sharded && getenv("PILCO_JAC_COPY") == nullptr;
     plan.jrec = jdirect ? h_jrec : ctx->jrec.p;
     plan.jstride = JS;
-    plan.jsmall = sharded ? 0 : jac_small_chunks(ctx, plan, H);
     double* h_misc = dev ? h_traj + NTJ : h_jrec + (size_t)H * JSg;
     double* h_all = h_misc + 8;                          // sharded: [W][H][PLcap * recp | E * reco]
-    int rr = -1;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    auto upload = [&]() -> int {
         HIPCHK(hipMemcpyAsync(plan.st[0], m0, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
         HIPCHK(hipMemcpyAsync(plan.st[0] + E, S0, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
-        rr = run_rollout(ctx, plan, H);
-        if (rr == -1) continue;
-        if (rr != PILCO_OK) return rr;
-        break;
-    }
-    if (rr == -1) return fail(ctx, PILCO_E_STATE, "rollout: the launch sequence was captured twice and never ran");
+        return PILCO_OK;
+    };
+    if (int r = run_rollout(ctx, plan, H, upload)) return r;   // (plan.route: the steps' layout the finish reads)
     if (!dev) HIPCHK(hipMemcpyAsync(h_misc, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
     if (dev) {
         // ---- the reverse chain on the device (rev.hip): nothing but the reward, the gradient -- and, for a caller with

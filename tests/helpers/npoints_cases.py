@@ -4,7 +4,7 @@ the host geometry, stream-K partition invariants, coverage guard, sensitivity of
 
 After padding to npad = round_up(n, 64) the launch geometry of a step follows from npad and the output count.  The functions
 below restate the host functions that choose it (csrc/prep.hip mm_prep_chunks, csrc/pair.hip pair_njb / mm_pair_nt /
-mm_pair_sk_steps, the stream-K cut of csrc/api.hip build_work, csrc/rollout.hip small_col_splits / jac_small_chunks,
+mm_pair_sk_steps, the stream-K cut of csrc/api.hip build_work, csrc/rollout.hip small_col_splits / plan_route,
 csrc/bwd.hip mm_bwd_geometry); test_npoints_cpu.py compiles the real ones and compares.  `cus` is the CU count (256 on MI355X),
 `cap` the stream-K capacity of the pair kernel's instantiation (resident waves: occupancy x CUs x 4).
 
