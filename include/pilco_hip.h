@@ -160,7 +160,10 @@ int pilco_rollout_batch(pilco_ctx* ctx, int B, const pilco_policy* policies, con
 int pilco_propagate(pilco_ctx* ctx, const pilco_policy* policy, const double* m_x, const double* s_x, double* M_x, double* S_x);
 /* controller.compute_action(m, s, squash) -> M (1,U), S (U,U), V (E,U)
  * (pilco/controllers.py:46-58,108-121) and reward.compute_reward(m,s) ->
- * muR, sR (pilco/rewards.py:19-51,58-61,73-81), evaluated on the device. */
+ * muR, sR (pilco/rewards.py:19-51,58-61,73-81), evaluated on the device.
+ * policy_action bounds state_dim and control_dim separately (each <= 32): state_dim + control_dim may exceed the 32 of a
+ * rollout, up to what the link's buffers allow in 160 KB of LDS -- (20, 20) and (32, 8) are supported, (32, 32) is refused
+ * with PILCO_E_SHAPE before any launch. */
 int pilco_policy_action(pilco_ctx* ctx, const pilco_policy* policy, const double* m, const double* s, double* M, double* S, double* V);
 int pilco_reward_eval(pilco_ctx* ctx, const pilco_reward_term* rewards, int n_rewards, int state_dim, const double* m, const double* s, double* muR, double* sR);
 

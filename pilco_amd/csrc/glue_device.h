@@ -2,6 +2,7 @@
 // fused head k_mm_prep<DT, true> (prep.hip).  Internal; gfx950 only.
 #pragma once
 #include "mm_device.h"
+#include "link_predicates.h"
 
 namespace pilco {
 
@@ -119,7 +120,7 @@ __device__ __forceinline__ void multi_load(double* lds, const LoadSeg (&sg)[NSEG
 // leave them in sc_alt -- the caller combines them where it needs them (write_joint_lin_squash below).
 __device__ __forceinline__ void squash_inplace(const GlueLds& L, int U, const double* maxact, double* cdiag, double* sc_alt = nullptr, bool eval_only = false) {
     const int t = threadIdx.x;
-    const int nm = L.nm, nm_sq = nm * nm;
+    const int nm = L.nm;
     // ONE inlined copy of each library function (exp, cos, sin), whatever element a thread evaluates: the argument and
     // the function are selected first.  (The first version had a copy per branch and a second, sequential code path for
     // large U -- 14 inlined transcendental bodies, ~20 KB of a link whose instruction stream is on the step's critical
@@ -127,7 +128,7 @@ __device__ __forceinline__ void squash_inplace(const GlueLds& L, int U, const do
     // cos(m_u -+ m_v) per element; exp, cos, sin per control) are independent: each goes to its own thread, in rounds when
     // the scratch (t1 .. js: 4 nm^2 + nm values) is smaller than that; then one combining phase per round.
     double* sc = sc_alt ? sc_alt : L.t1;
-    const int cap = sc_alt ? 5 * (U * U + U) : ((4 * nm_sq + nm) / 5) * 5;      // whole items per round: an item is 5 slots (a control uses 3 of its 5)
+    const int cap = sc_alt ? 5 * (U * U + U) : PILCO_SQUASH_ROUND_CAP(nm);      // whole items per round: an item is 5 slots (a control uses 3 of its 5)
     const int nitems = U * U + U;                    // items 0 .. U^2 - 1: covariance elements, then the U controls
     // the new covariance must not overwrite su while later rounds still read it: it is collected in registers per thread
     // (element e = t + k * blockDim of the U x U matrix; U <= 32, blockDim >= 256: k < 4) and stored after the last round
@@ -508,30 +509,7 @@ __device__ __forceinline__ void xq_push(const GlueArgs& g, const double* seg_lds
 // Same formulas as prep_device.h / pair_device.h (their comments cite the reference lines), plain fp64 `exp`.
 // Every reduction is done by threads 0..255 in a fixed order, whatever the workgroup size: all workgroups of a head -- and
 // k_glue -- produce the same bits.
-struct RbfInlineLayout {
-    int ctr, bet, il, var, lvar, aug0, aug1, piv, T, Q, det, pt, red, red3, total;
-};
-__host__ __device__ inline RbfInlineLayout rbf_inline_layout(int E, int U, int bf) {
-    const int P = U * (U + 1) / 2, nmat = U + P;
-    RbfInlineLayout l;
-    int o = 0;
-    l.ctr = o; o += bf * E;                 // centred centres  zeta_i = c_i - m
-    l.bet = o; o += U * bf;                 // beta of every output
-    l.il = o;  o += U * E;                  // 1 / lengthscale
-    l.var = o; o += U;
-    l.lvar = o; o += U;                     // log of the signal variances (phase 3's exponents)
-    l.aug0 = o; o += nmat * E * 2 * E;      // augmented matrices of the batched Gauss-Jordan (ping)
-    l.aug1 = o; o += nmat * E * 2 * E;      //                                                (pong)
-    l.piv = o; o += nmat * E;               // pivots -> determinants
-    l.T = o;   o += U * E * E;              // T_u = (s + Lambda_u^2)^-1
-    l.Q = o;   o += P * E * E;              // Q_uv = R_uv^-1 s / 2
-    l.det = o; o += nmat;                   // det B_u | det R_uv
-    l.pt = o;  o += bf * (2 * E + 2) + bf * 16;   // per point of the current pair: u_i, v_i, p_i = 2 Q z_i, w_i | 16 doubles of scratch per point
-    l.red = o; o += 4 * (E + 2);            // wave partials (mean part)
-    l.red3 = o; o += 4;                     // wave partials (covariance part: it may run beside the mean part)
-    l.total = (o + 1) & ~1;
-    return l;
-}
+// (RbfInlineLayout / rbf_inline_layout: link_predicates.h)
 
 // The policy GP's constants (raw centres, transposed as stored: [E][bf]; beta [U][bf]; lengthscales [U][E]; variances [U])
 // into LDS.  Issued together with the link's first batch of loads, so that their memory round trip is the link's own.
@@ -1027,7 +1005,7 @@ __device__ __forceinline__ void glue_body(const GlueArgs& g, const GlueLds& L, b
             if (g.squash) {
                 double* cdiag = L.misc + 1;  // [U]
                 // the joint Gaussian is what follows and the evaluations fit t2: stop behind them (write_joint_lin_squash)
-                lin_fused = !g.act_out && !joint_is_state && 5 * (U * U + U) <= L.nm * L.nm;
+                lin_fused = !g.act_out && !joint_is_state && PILCO_SQUASH_LIN_FUSED_FITS(U, L.nm);
                 squash_inplace(L, U, g.maxact ? L.misc + 160 : nullptr, cdiag, lin_fused ? L.t2 : nullptr, lin_fused);
                 if (g.act_out) {
                     for (int e = t; e < E * U; e += blockDim.x) L.cxu[e] *= cdiag[e % U];   // V @ C, C diagonal

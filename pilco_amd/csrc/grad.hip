@@ -1,6 +1,7 @@
 // Reverse mode: the VJP of one moment-matching step (device) and the native reverse sweep of a rollout
 // (DESIGN.md section 9).
 #include "ctx.h"
+#include "reward_factor.h"
 
 extern "C" {
 
@@ -195,7 +196,11 @@ bool reward_grad(const pilco_reward_term* rw, int n_rw, int E, const double* m, 
         vec dTi(E, 0.0);   // d^T iSpW
         for (int j = 0; j < E; ++j)
             for (int i = 0; i < E; ++i) dTi[j] += d[i] * iSpW[(size_t)i * E + j];
-        for (int j = 0; j < E; ++j) dm[j] -= c * muR * dTi[j];
+        // d (d^T X d) / d d = (X + X^T) d.  X = iSpW is symmetric with W: a weight on the factored path (psd_factor's rank >= 0,
+        // the device chain's criterion) keeps the one-sided form and its bits, a weight on the general path may be asymmetric
+        std::vector<double> Fu;
+        const bool general = W && pilco::psd_factor(W, E, Fu) < 0;
+        for (int j = 0; j < E; ++j) dm[j] -= c * muR * (general ? 0.5 * (v[j] + dTi[j]) : dTi[j]);
         // dS = muR (iSpW d d^T - I) iSpW / 2, symmetrised
         vec T((size_t)E * E);
         for (int i = 0; i < E; ++i)
@@ -694,7 +699,7 @@ int rollout_grad_finish(pilco_ctx* ctx, const pilco_policy* policy, const pilco_
     const size_t JS = gc.JS;
     const auto tm0 = gc.tm0, tm1 = gc.tm1;
     vec e(U);
-    for (int u = 0; u < U; ++u) e[u] = policy->max_action[u];
+    for (int u = 0; u < U; ++u) e[u] = policy->max_action ? policy->max_action[u] : 1.0;   // (NULL = ones, as the forward pass takes it)
     vec mbar(E, 0.0), sbar((size_t)E * E, 0.0);
     // An objective beyond the additive reward (Safe-PILCO's multiplicative risk term, any function of the state
     // trajectory): the caller turns the trajectory into cotangent seeds d objective / d (m_t, s_t), t = 0..H, and the

@@ -68,7 +68,9 @@ __device__ inline void rev_local_step(int n, const RevRewards& rs, int E, int U,
         double quad = 0.0;
         for (int i = 0; i < E; ++i) quad = fma(d[i], v[i], quad);
         const double muR = exp(-0.5 * quad) / sqrt(det);
-        if (t < E) dm[t] -= c * muR * dTi[t];
+        // d (d^T X d) / d d = (X + X^T) d.  X is symmetric with W, and a symmetric PSD weight (rank >= 0) keeps the one-sided
+        // form and its bits; a weight on the general path may be asymmetric, where d^T X alone is wrong (rw_asym: 5 %)
+        if (t < E) dm[t] -= c * muR * (rw.rank >= 0 ? dTi[t] : 0.5 * (v[t] + dTi[t]));
         for (int e = t; e < E * E; e += 256) {
             const int i = e / E, j = e - i * E;
             const double Tij = 0.5 * muR * (v[i] * dTi[j] - res[j * nc + E + i]);

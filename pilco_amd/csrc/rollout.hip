@@ -1,65 +1,12 @@
 // Rollouts (PILCO.predict / propagate, pilco/models/pilco.py:118-153): plan, launch sequence, hipGraph capture
 // and replay, and the policy / reward evaluation entry points.
 #include "ctx.h"
+#include "reward_factor.h"
 #include <chrono>
 
 namespace {
 
-// W (E x E, symmetric PSD) = F F^T with F (E x rank) from a cyclic Jacobi eigen-decomposition.
-// Returns rank, or -1 when W is not symmetric PSD (the general pivoted device path is used then).
-int psd_factor(const double* W, int E, std::vector<double>& F) {
-    double scale = 0.0;
-    for (int i = 0; i < E * E; ++i) scale = std::max(scale, std::fabs(W[i]));
-    if (scale == 0.0) { F.clear(); return 0; }
-    for (int i = 0; i < E; ++i)
-        for (int j = 0; j < i; ++j)
-            if (std::fabs(W[i * E + j] - W[j * E + i]) > 1e-13 * scale) return -1;
-    std::vector<double> A(W, W + E * E), V(E * E, 0.0);
-    for (int i = 0; i < E; ++i) V[i * E + i] = 1.0;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0;
-        for (int i = 0; i < E; ++i)
-            for (int j = 0; j < i; ++j) off += A[i * E + j] * A[i * E + j];
-        if (off <= 1e-32 * scale * scale) break;
-        for (int p = 0; p < E; ++p)
-            for (int q = p + 1; q < E; ++q) {
-                const double apq = A[p * E + q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q * E + q] - A[p * E + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-                for (int k = 0; k < E; ++k) {
-                    const double akp = A[k * E + p], akq = A[k * E + q];
-                    A[k * E + p] = c * akp - sn * akq;
-                    A[k * E + q] = sn * akp + c * akq;
-                }
-                for (int k = 0; k < E; ++k) {
-                    const double apk = A[p * E + k], aqk = A[q * E + k];
-                    A[p * E + k] = c * apk - sn * aqk;
-                    A[q * E + k] = sn * apk + c * aqk;
-                }
-                for (int k = 0; k < E; ++k) {
-                    const double vkp = V[k * E + p], vkq = V[k * E + q];
-                    V[k * E + p] = c * vkp - sn * vkq;
-                    V[k * E + q] = sn * vkp + c * vkq;
-                }
-            }
-    }
-    double lmax = 0.0;
-    for (int i = 0; i < E; ++i) lmax = std::max(lmax, A[i * E + i]);
-    for (int i = 0; i < E; ++i)
-        if (A[i * E + i] < -1e-12 * std::max(lmax, scale)) return -1;
-    std::vector<int> keep;
-    for (int i = 0; i < E; ++i)
-        if (A[i * E + i] > 1e-15 * lmax) keep.push_back(i);
-    const int r = (int)keep.size();
-    F.assign((size_t)E * std::max(r, 1), 0.0);
-    for (int k = 0; k < r; ++k) {
-        const double sq = std::sqrt(A[keep[k] * E + keep[k]]);
-        for (int e = 0; e < E; ++e) F[(size_t)e * r + k] = V[e * E + keep[k]] * sq;
-    }
-    return r;
-}
+constexpr size_t GLUE_LDS_LIMIT = 160 * 1024;   // bytes of LDS a workgroup can have on gfx950
 
 // marshal reward terms into a host staging vector; pointers are patched relative to dev_base
 int stage_rewards(pilco_ctx* ctx, const pilco_reward_term* rw, int n_rw, int E, std::vector<double>& hp, size_t& off,
@@ -78,7 +25,7 @@ int stage_rewards(pilco_ctx* ctx, const pilco_reward_term* rw, int n_rw, int E, 
             else std::fill(hp.begin() + off, hp.begin() + off + E, 0.0);
             out[i].t = dev_base + off; off += E;
             std::vector<double> F;
-            const int r = psd_factor(rw[i].W, E, F);
+            const int r = pilco::psd_factor(rw[i].W, E, F);   // (reward_factor.h)
             out[i].rank = r;
             if (r > 0) {
                 memcpy(&hp[off], F.data(), sizeof(double) * E * r);
@@ -875,6 +822,12 @@ int pilco_propagate(pilco_ctx* ctx, const pilco_policy* policy, const double* m_
     return pilco_rollout(ctx, policy, nullptr, 0, m_x, s_x, 1, M_x, S_x, &r, nullptr);
 }
 
+// Shapes: state_dim and control_dim are bounded SEPARATELY (each <= 32), so D = E + U may reach 64 here, twice what a rollout
+// takes.  The link's code is sound for that (every misc[] slot is indexed by E or by U alone, the square buffers are carved
+// with nm = D, squash_inplace keeps U^2 <= 1024 elements in 4 registers per thread), so 32 < D <= 64 IS supported -- as far as
+// k_glue's buffers fit the 160 KB of LDS a workgroup can have (7 D^2 + 3 D + 256 doubles and the reward scratch: (20, 20)
+// and (32, 8) fit, (32, 32) would need 275 KB).  A shape that does not fit is refused with PILCO_E_SHAPE before anything
+// is copied or launched (tests/test_gpu_link_edges.py holds both answers).
 int pilco_policy_action(pilco_ctx* ctx, const pilco_policy* policy, const double* m, const double* s_in, double* M, double* S, double* V) {
     if (!ctx) return PILCO_E_SHAPE;
     if (!policy || !m || !s_in || !M || !S || !V) return fail(ctx, PILCO_E_SHAPE, "policy_action: null pointer");
@@ -904,13 +857,14 @@ int pilco_policy_action(pilco_ctx* ctx, const pilco_policy* policy, const double
         g.squash = policy->squash;
         g.pwk = ps.wk;
         g.pvar = ps.var.p;
+        g.flags = GF_RBF_POST | GF_POLICY;
+        if (sizeof(double) * glue_lds_doubles_for(g) > GLUE_LDS_LIMIT) return fail(ctx, PILCO_E_SHAPE, "policy_action: state_dim + control_dim too large for the link's LDS");
         HIPCHK(hipMemcpyAsync(ctx->state.p, h.data(), sizeof(double) * n_st, hipMemcpyHostToDevice, ctx->st));
         HIPCHK(hipMemcpyAsync(ps.wk.in_m, m, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
         HIPCHK(hipMemcpyAsync(ps.wk.in_s, s_in, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
         const MMModel pmd = model_of(ps);
         launch_mm_prep(ctx->st, pmd, ps.wk);
         launch_mm_pair(ctx->st, pmd, ps.wk, ctx->variant);
-        g.flags = GF_RBF_POST | GF_POLICY;
         launch_glue(ctx->st, g);
         std::vector<double> o((size_t)U + U * U + (size_t)E * U);
         HIPCHK(hipMemcpyAsync(o.data(), g.act_out, sizeof(double) * o.size(), hipMemcpyDeviceToHost, ctx->st));
@@ -922,6 +876,7 @@ int pilco_policy_action(pilco_ctx* ctx, const pilco_policy* policy, const double
         return PILCO_OK;
     }
     if (!policy->W || !policy->b) return fail(ctx, PILCO_E_SHAPE, "policy_action: linear policy needs W and b");
+    if (glue_lds_bytes(E, E + U) > GLUE_LDS_LIMIT) return fail(ctx, PILCO_E_SHAPE, "policy_action: state_dim + control_dim too large for the link's LDS");
     const size_t n_state = (size_t)E + E * E + (size_t)U * E + 2 * U + (U + U * U + (size_t)E * U);
     ENSURE(ctx->state, n_state + 8);
     std::vector<double> h(n_state, 0.0);
