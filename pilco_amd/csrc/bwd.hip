@@ -1,4 +1,5 @@
 // Reverse pass of one moment-matching step: k_mm_bwd_pair / _post / _fin.
+#include "grad_layout.h"
 #include "mm_device.h"
 #include "rev_local.h"
 
@@ -1234,10 +1235,7 @@ __global__ __launch_bounds__(256, JAC_REC_LB) void k_mm_jac_rec(MMModel md, MMWo
     JAC_STAMP(wk, 53, pl == 0 && z == 0 && t == 0);
 }
 
-size_t mm_jac_rec_size(int D, int E, int P) {
-    const size_t NT2 = (size_t)D * (D + 1) / 2;
-    return (size_t)P * (1 + D + NT2) + (size_t)E * (D + NT2 + (size_t)D * D + D * NT2);
-}
+size_t mm_jac_rec_size(int D, int E, int P) { return jac_rec_size(D, E, P); }   // (grad_layout.h)
 size_t mm_jac_part_size(int D, int E, int P, int npad) {
     return (size_t)P * mm_bwd_rc(npad) * (1 + D + D * D) + (size_t)E * mm_bwd_rc(npad) * mm_jac_ns(D);
 }

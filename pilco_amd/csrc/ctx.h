@@ -1,5 +1,5 @@
 // Internal state of libpilco_hip.so shared by its host-side translation units (api.hip, rollout.hip, shard.hip,
-// grad.hip): the context and GP-slot structs, the error / allocation macros and the cross-file helpers.
+// grad_route.hip, grad.hip): the context and GP-slot structs, the error / allocation macros and the cross-file helpers.
 #pragma once
 #include <rccl/rccl.h>
 
@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "grad_layout.h"
 #include "moment.h"
 
 using namespace pilco;
@@ -151,8 +152,7 @@ struct pilco_ctx {
     bool dev_chain = true;   // LinearController gradients: the reverse chain runs on the device (false: the host chain of rounds 1-5, kept for the RbfController and as a cross-check)
     double* jpin = nullptr;  // pinned host copy of (traj | tape | jrec) for the host-side reverse sweep
     size_t jpin_cap = 0;
-    hipEvent_t jwait_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // behind the chunks of the records' download (last steps first)
-    int jwait_t0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, jwait_n = 0, jwait_next = 0, jwait_from = 0;   // first step of chunk k; steps >= jwait_from are on the host
+    hipEvent_t jwait_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // behind the chunks of the records' download (last steps first); reused from call to call, the chunks' state is the call's (GradCall)
     DevBuf selftest;
     DevBuf exp_tab;  // 2^(j/n), j = 0..n-1, n = mm_exp_table_size(), high words biased (mm_exp_table_fill)
     unsigned long long* dbg = nullptr;   // [PILCO_DBG_WORDS] developer stamps (pilco_debug_timestamps allocates it)
@@ -280,31 +280,83 @@ struct RolloutPlan {
     size_t jstride = 0;
     StepRoute route;
 };
-constexpr int PILCO_JAC_TOO_LARGE = -77;   // rollout_jtape: the per-step buffers would exceed the cap (caller falls back)
-// Device reverse chain of a LinearController's gradient: what rollout_jtape(.., dev) leaves enqueued / staged.
-struct JtapeDev {
-    bool seeds = false;                 // the caller has cotangent seeds to add: the chain kernel is launched by rollout_jtape_dev_finish, behind their upload
-    RevArgs ra{};
-    size_t n_seeds = 0, n_out = 0;
-    double* h_seeds = nullptr;          // pinned staging [H + 1][E + E*E]
-    const double* h_out = nullptr;      // pinned: dW | db | status | d / d (m_0, S_0), written by the chain kernel
-    const double* h_traj = nullptr;     // pinned trajectory (seeds only; valid once jwait_ev[0] has passed)
-    const double* h_reward = nullptr;   // pinned reward (valid with h_out)
+int rollout_run(pilco_ctx* ctx, RolloutPlan& plan, int H, const double* m0, const double* S0);   // run_rollout with (m0, S0) uploaded from the caller's memory
+// grad_route.hip
+// The route of one value-and-gradient rollout, decided before anything is enqueued (plan_grad): which reverse chain runs,
+// how the ranks exchange their Jacobian records, whether the caller adds cotangent seeds.  Everything after the plan
+// branches on this and on nothing else; the route record's gradient words are written from it (grad_route_record).
+enum GradChain {
+    GRAD_CHAIN_DEVICE,    // Jacobian records, reverse chain on the device (rev.hip): ROUTE_CHAIN 1, ROUTE_TAPE 2
+    GRAD_CHAIN_RECORDS,   // Jacobian records, reverse chain on the host over them (grad.hip: jac_vjp): ROUTE_CHAIN 2, ROUTE_TAPE 2
+    GRAD_CHAIN_ADJOINT,   // plain tape, host chain with the device adjoint of every step (pilco_gp_predict_vjp): ROUTE_CHAIN 2, ROUTE_TAPE 1
 };
-typedef void (*jtape_seed_fn)(void* user, int H, int E, const double* traj, double* seeds);
-int rollout_jtape_dev_finish(pilco_ctx* ctx, JtapeDev& dev, int H, int E, jtape_seed_fn seed_fn, void* seed_user);
-int rollout_jtape_wait(pilco_ctx* ctx, int t);   // blocks until the records of step t have arrived
-// forward rollout with the tape and the Jacobian records of every step, downloaded into pinned memory (grad.hip)
-int rollout_jtape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* m0,
-                  const double* S0, int H, double* reward, const double** traj, const double** tape, const double** jrec, size_t* jstride,
-                  const double** reward_later = nullptr,    // reward_later: return without waiting (one rank); *reward_later is valid once rollout_jtape_wait(ctx, H - 1) has returned
-                  JtapeDev* dev = nullptr);                 // dev: records stay on the device, the reverse chain runs there (LinearController); returns without waiting
+enum GradExchange { GRAD_XCH_NONE, GRAD_XCH_COMM, GRAD_XCH_GROUP };   // one rank (or no steps) / RCCL all-gather / contexts of one process between host barriers
+struct GradRoute {
+    GradChain chain = GRAD_CHAIN_RECORDS;
+    GradExchange exchange = GRAD_XCH_NONE;
+    bool seeds = false;   // the caller brings cotangent seeds (device chain: the chain kernel waits for their upload)
+    int rev_lds = 0;      // ROUTE_REV_LDS
+};
+// One value-and-gradient rollout between its two halves: grad_forward enqueues the forward half along the route and says where
+// its results land, the chain's finish (grad.hip: rollout_grad_finish, or grad_device_finish) picks them up.  Several can be
+// in flight at once (the lanes of a batch call).
+struct GradCall {
+    GradRoute route;
+    RolloutPlan plan;
+    int H = 0;
+    // host chains: trajectory [H + 1][E + E*E], tape [H][tape_rec.size], records [H][JS] and the reward (pinned memory; the
+    // plain tape: traj_v / tape_v).  arrived: reward, trajectory, tape and the records of the last steps are on the host
+    double *traj = nullptr, *tape = nullptr, *jrec = nullptr, *reward = nullptr;
+    size_t JS = 0;
+    std::vector<double> traj_v, tape_v;
+    bool arrived = false;
+    // the records' download in chunks, last steps first, an event of ctx->jwait_ev behind each: chunk k starts at step
+    // wait_t0[k]; the steps >= wait_from are on the host (grad_wait)
+    int wait_t0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wait_n = 0, wait_next = 0, wait_from = 0;
+    // device chain: the chain's arguments (launched by the forward half, or -- seeds -- by the finish behind their upload),
+    // pinned staging of the seeds [H + 1][E + E*E] and the chain's output vector (rev_out)
+    RevArgs ra{};
+    size_t n_seeds = 0;
+    double* h_seeds = nullptr;
+    const double* h_out = nullptr;
+    std::chrono::steady_clock::time_point tm0, tm1;   // PILCO_GRAD_TIMING
+};
+int plan_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, int H, bool linear, bool seeds,
+              const GradRoute* decided, GradCall& gc);   // decided: a further lane of a batch call takes lane 0's route
+int grad_forward(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* m0, const double* S0,
+                 double* reward, bool defer, GradCall& gc);
+int grad_arrive(pilco_ctx* ctx, GradCall& gc, double* reward);   // host chains: blocks until the forward half's results are on the host
+int grad_wait(pilco_ctx* ctx, GradCall& gc, int t);              // ... until the records of step t are
+int grad_device_finish(pilco_ctx* ctx, GradCall& gc, pilco_seed_fn seed_fn, void* seed_user, double* reward, double* dW, double* db);
+void grad_route_record(pilco_ctx* ctx, const GradRoute& route);
 int rollout_lanes(pilco_ctx* ctx, int B, std::vector<pilco_ctx*>& lane, const char* who);   // lanes of a batch call (rollout.hip)
 void rollout_lanes_done(pilco_ctx* ctx);   // ... and after it: the context is on its own again
 struct LanesGuard {
     pilco_ctx* c;
     ~LanesGuard() { rollout_lanes_done(c); }
 };
+// The calls of a batch: begin(i) enqueues lane i's work and returns without waiting, for every lane in turn until one fails;
+// then finish(i) waits for and completes every lane that began -- lane i's host work runs while lanes i + 1.. are still on the
+// device.  The first error is the call's, labelled with its lane on ctx.  drain: after an error nothing may stay in
+// flight behind the caller's back -- every lane's stream is waited for.
+template <class Begin, class Finish>
+int run_lanes(pilco_ctx* ctx, const std::vector<pilco_ctx*>& lane, bool drain, Begin&& begin, Finish&& finish) {
+    const int B = (int)lane.size();
+    int err = PILCO_OK, begun = 0;
+    auto note = [&](int i, int r) {
+        if (!r || err) return;
+        err = r;
+        if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
+    };
+    for (; begun < B; ++begun) {
+        note(begun, begin(begun));
+        if (err) break;
+    }
+    for (int i = 0; i < begun; ++i) note(i, finish(i));
+    if (err && drain)
+        for (pilco_ctx* l : lane) (void)hipStreamSynchronize(l->st);
+    return err;
+}
 int setup_rollout(pilco_ctx* ctx, const pilco_policy* pol, const pilco_reward_term* rw, int n_rw, int H, bool want_traj,
                   RolloutPlan& plan);
 // shard.hip: peer exchange

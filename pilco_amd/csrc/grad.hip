@@ -608,7 +608,8 @@ void jac_vjp(const double* __restrict__ jr, int D, int E, const double* M, const
             for (int e = 0; e < n; e += 8) __builtin_prefetch(x + e + pf, 0, 1);
         for (int e = 0; e < n; ++e) y[e] += c * x[e];
     };
-    const int nI = D * D, NT2 = D * (D + 1) / 2, recp = 1 + D + NT2, P = E * (E + 1) / 2;
+    const RevDims dm = rev_dims(E, D - E, D);   // (grad_layout.h: the records' layout)
+    const int nI = dm.nI, NT2 = dm.NT2, recp = dm.recp, P = dm.P;
     acc.assign((size_t)D + NT2, 0.0);
     double* __restrict__ am = acc.data();
     // pairs in the dealing order: (0,0) .. (E-1,E-1), (1,0), (2,0), (2,1), ...
@@ -623,7 +624,7 @@ void jac_vjp(const double* __restrict__ jr, int D, int E, const double* M, const
     for (int a = 1; a < E; ++a)
         for (int b = 0; b < a; ++b) add_pair(a, b);
     const double* jo = jr + (size_t)P * recp;
-    const size_t reco = (size_t)D + NT2 + nI + (size_t)D * NT2;
+    const size_t reco = (size_t)dm.reco;
     for (int a = 0; a < E; ++a) {
         double mu = Mbar[a];
         for (int b = 0; b < E; ++b) mu -= (Sbar[(size_t)a * E + b] + Sbar[(size_t)b * E + a]) * M[b];
@@ -642,59 +643,17 @@ void jac_vjp(const double* __restrict__ jr, int D, int E, const double* M, const
         for (int r = 0; r <= c; ++r) sbar[(size_t)r * D + c] = sbar[(size_t)c * D + r] = am[D + (size_t)c * (c + 1) / 2 + r];
 }
 
-// In two halves, so that several value-and-gradient rollouts (the lanes of pilco_rollout_grad_batch) can be in flight at once:
-// rollout_grad_begin enqueues the forward half -- with `defer` it returns without waiting for anything -- and
-// rollout_grad_finish waits for the records chunk by chunk while it runs the host's reverse sweep.
-struct GradCall {
-    bool jac = false;
-    const double *traj = nullptr, *tape = nullptr, *jrec = nullptr, *reward_later = nullptr;
-    size_t JS = 0;
-    vec traj_v, tape_v;
-    std::chrono::steady_clock::time_point tm0, tm1;
-};
-int rollout_grad_begin(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* m0,
-                       const double* S0, int H, double* reward, GradCall& gc, bool defer) {
-    const int E = policy->state_dim, U = policy->control_dim, D = E + U;
-    const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
-    // Forward half.  Jacobian tape (default): one O(N^2) sweep per step gives the value and the step's Jacobian records,
-    // the reverse sweep below is host algebra only.  PILCO_GRAD_MODE=0 / pilco_set_grad_mode(ctx, 0): plain tape, and
-    // the O(N^2) adjoint of every step on the device again (pilco_gp_predict_vjp) -- the two agree to rounding.
-    bool jac = ctx->grad_mode != 0;
-    gc.tm0 = std::chrono::steady_clock::now();
-    vec mH(E), SH((size_t)E * E);
-    if (jac) {
-        const int r = rollout_jtape(ctx, policy, rewards, n_rewards, m0, S0, H, reward, &gc.traj, &gc.tape, &gc.jrec, &gc.JS,
-                                    defer ? &gc.reward_later : nullptr);
-        if (r == PILCO_JAC_TOO_LARGE) jac = false;
-        else if (r) return r;
-    }
-    if (!jac) {   // (runs to completion here: nothing of it overlaps with other lanes)
-        gc.traj_v.resize((size_t)(H + 1) * (E + E * E));
-        gc.tape_v.resize(std::max<size_t>(1, (size_t)H * TS));
-        if (int r = pilco_rollout_tape(ctx, policy, rewards, n_rewards, m0, S0, H, mH.data(), SH.data(), reward, gc.traj_v.data(), gc.tape_v.data()))
-            return r;
-        gc.traj = gc.traj_v.data();
-        gc.tape = gc.tape_v.data();
-    }
-    gc.jac = jac;
-    gc.tm1 = std::chrono::steady_clock::now();
-    return PILCO_OK;
-}
-int rollout_grad_finish(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, int H, double* reward,
+// The host's reverse chain, the second half of a value-and-gradient rollout whose route is not the device chain: it
+// waits for the forward half (grad_route.hip: grad_forward) and then -- chunk by chunk -- for the records while it walks the
+// steps backwards.  In two halves so that several rollouts (the lanes of a batch call) can be in flight at once.
+int rollout_grad_finish(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, double* reward,
                         PolicyAdj& pol, pilco_seed_fn seed_fn, void* seed_user, GradCall& gc) {
-    const int E = policy->state_dim, U = policy->control_dim, D = E + U;
-    ctx->route[ROUTE_ENTRY] = 2;   // pilco_debug_last_route: the host chain
-    ctx->route[ROUTE_CHAIN] = 2;
-    ctx->route[ROUTE_REV_LDS] = 0;
-    const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
-    const bool jac = gc.jac;
+    const int E = policy->state_dim, U = policy->control_dim, D = E + U, H = gc.H;
+    grad_route_record(ctx, gc.route);
+    const TapeRec tr = tape_rec(D, E);
+    const bool jac = gc.route.chain == GRAD_CHAIN_RECORDS;
     const bool timing = getenv("PILCO_GRAD_TIMING") != nullptr;   // developer aid: forward / reverse split on stderr
-    if (gc.reward_later) {   // deferred begin: the reward, the trajectory, the tape and the last chunk of records
-        if (int r = rollout_jtape_wait(ctx, H - 1)) return r;
-        if (H <= 0) HIPCHK(hipStreamSynchronize(ctx->st));
-        *reward = *gc.reward_later;
-        gc.tm1 = std::chrono::steady_clock::now();
-    }
+    if (int r = grad_arrive(ctx, gc, reward)) return r;
     const double *traj = gc.traj, *tape = gc.tape, *jrec = gc.jrec;
     const size_t JS = gc.JS;
     const auto tm0 = gc.tm0, tm1 = gc.tm1;
@@ -724,12 +683,12 @@ int rollout_grad_finish(pilco_ctx* ctx, const pilco_policy* policy, const pilco_
     for (int t = H - 1; t >= 0; --t) {
         const double* m_x = &traj[(size_t)t * (E + E * E)];
         const double* s_x = m_x + E;
-        const double* rec = &tape[(size_t)t * TS];
-        const double* m_j = rec;
-        const double* s_j = rec + D;
-        const double* s1 = rec + D + D * D;                                      // (E, D)
-        const double* Mgp = rec + D + D * D + (size_t)E * D;                     // (E)   GP means of the step
-        const double* V = rec + D + D * D + (size_t)E * D + E + (size_t)E * E;   // (D, E)
+        const double* rec = &tape[(size_t)t * tr.size];
+        const double* m_j = rec + tr.m_j;
+        const double* s_j = rec + tr.s_j;
+        const double* s1 = rec + tr.s1;    // (E, D)
+        const double* Mgp = rec + tr.M;    // (E)   GP means of the step
+        const double* V = rec + tr.V;      // (D, E)
         // propagate (pilco.py:147-149): M_x = M + m_x, S_x = S + s_x + s1 V + (s1 V)^T
         for (int i = 0; i < E; ++i)
             for (int j = 0; j < E; ++j) G[(size_t)i * E + j] = sbar[(size_t)i * E + j] + sbar[(size_t)j * E + i];
@@ -748,9 +707,9 @@ int rollout_grad_finish(pilco_ctx* ctx, const pilco_policy* policy, const pilco_
         mxb = mbar;
         sxb = sbar;
         if (jac) {
-            if (int r = rollout_jtape_wait(ctx, t)) return r;
+            if (int r = grad_wait(ctx, gc, t)) return r;
             jac_vjp(jrec + (size_t)t * JS, D, E, Mgp, mbar.data(), sbar.data(), Vb.data(), mjb.data(), sjb.data(), jacc,
-                    (t > 0 && t - 1 >= ctx->jwait_from) ? -(long)JS : 0);   // (only records that have arrived)
+                    (t > 0 && t - 1 >= gc.wait_from) ? -(long)JS : 0);   // (only records that have arrived)
             for (int q = 0; q < D * D; ++q)
                 if (!std::isfinite(sjb[q])) return fail(ctx, PILCO_E_NOT_PD, "rollout_grad: singular s + Lambda^2 or I + Lambda s");
         } else if (int r = pilco_gp_predict_vjp(ctx, PILCO_SLOT_DYNAMICS, m_j, s_j, mbar.data(), sbar.data(), Vb.data(), mjb.data(), sjb.data())) {
@@ -812,40 +771,12 @@ int rollout_grad_finish(pilco_ctx* ctx, const pilco_policy* policy, const pilco_
     }
     return PILCO_OK;
 }
-int rollout_grad_impl(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
-                      const double* m0, const double* S0, int H, double* reward, PolicyAdj& pol, pilco_seed_fn seed_fn, void* seed_user) {
-    GradCall gc;
-    if (int r = rollout_grad_begin(ctx, policy, rewards, n_rewards, m0, S0, H, reward, gc, false)) return r;
-    return rollout_grad_finish(ctx, policy, rewards, n_rewards, H, reward, pol, seed_fn, seed_user, gc);
-}
 
-// LinearController: the reverse chain on the device (rev.hip).  begin enqueues the forward half, the records' finish and --
-// unless the caller has cotangent seeds to add -- the chain itself, and returns without waiting; finish waits (with seeds:
-// trajectory -> callback -> upload -> chain -> wait).  PILCO_JAC_TOO_LARGE from begin: nothing was enqueued, the caller takes
-// the host chain.
-bool dev_chain_applies(const pilco_ctx* ctx, const pilco_policy* policy) {
-    const int E = policy->state_dim, U = policy->control_dim;
-    return ctx->dev_chain && ctx->grad_mode != 0 && E + U <= 14 && rev_chain_supported(E, U, E + U);
-}
-int rollout_grad_dev_begin(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* m0,
-                           const double* S0, int H, bool seeds, JtapeDev& dev) {
-    dev.seeds = seeds;
-    double r_unused = 0.0;
-    const double *t0 = nullptr, *t1 = nullptr, *t2 = nullptr;
-    size_t js = 0;
-    return rollout_jtape(ctx, policy, rewards, n_rewards, m0, S0, H, &r_unused, &t0, &t1, &t2, &js, nullptr, &dev);
-}
-int rollout_grad_dev_finish(pilco_ctx* ctx, JtapeDev& dev, const pilco_policy* policy, int H, pilco_seed_fn seed_fn, void* seed_user,
-                            double* reward, double* dW, double* db) {
-    const int E = policy->state_dim, U = policy->control_dim;
-    ctx->route[ROUTE_ENTRY] = 2;   // pilco_debug_last_route: the device chain
-    ctx->route[ROUTE_CHAIN] = 1;
-    ctx->route[ROUTE_REV_LDS] = (int)rev_step_lds_bytes(E, U, E + U);
-    if (int r = rollout_jtape_dev_finish(ctx, dev, H, E, seed_fn, seed_user)) return r;
-    *reward = *dev.h_reward;
-    memcpy(dW, dev.h_out, sizeof(double) * (size_t)U * E);
-    memcpy(db, dev.h_out + (size_t)U * E, sizeof(double) * (size_t)U);
-    return PILCO_OK;
+// One value-and-gradient rollout over the host chain, both halves
+int rollout_grad_host(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* m0,
+                      const double* S0, double* reward, PolicyAdj& pol, pilco_seed_fn seed_fn, void* seed_user, GradCall& gc) {
+    if (int r = grad_forward(ctx, policy, rewards, n_rewards, m0, S0, reward, false, gc)) return r;
+    return rollout_grad_finish(ctx, policy, rewards, n_rewards, reward, pol, seed_fn, seed_user, gc);
 }
 
 int check_grad_args(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, int kind) {
@@ -871,14 +802,14 @@ int pilco_rollout_grad_seeded(pilco_ctx* ctx, const pilco_policy* policy, const 
     if (!ctx) return PILCO_E_SHAPE;
     if (!policy || !m0 || !S0 || !reward || !dW || !db || H < 0) return fail(ctx, PILCO_E_SHAPE, "rollout_grad: bad arguments");
     if (int r = check_grad_args(ctx, policy, rewards, n_rewards, PILCO_POLICY_LINEAR)) return r;
-    if (dev_chain_applies(ctx, policy)) {
-        JtapeDev dev;
-        const int r = rollout_grad_dev_begin(ctx, policy, rewards, n_rewards, m0, S0, H, seed_fn != nullptr, dev);
-        if (r == PILCO_OK) return rollout_grad_dev_finish(ctx, dev, policy, H, seed_fn, seed_user, reward, dW, db);
-        if (r != PILCO_JAC_TOO_LARGE) return r;
+    GradCall gc;
+    if (int r = plan_grad(ctx, policy, rewards, n_rewards, H, true, seed_fn != nullptr, nullptr, gc)) return r;
+    if (gc.route.chain == GRAD_CHAIN_DEVICE) {
+        if (int r = grad_forward(ctx, policy, rewards, n_rewards, m0, S0, reward, false, gc)) return r;
+        return grad_device_finish(ctx, gc, seed_fn, seed_user, reward, dW, db);
     }
     LinearAdj pol(policy->state_dim, policy->control_dim, policy->W, policy->b);
-    if (int r = rollout_grad_impl(ctx, policy, rewards, n_rewards, m0, S0, H, reward, pol, seed_fn, seed_user)) return r;
+    if (int r = rollout_grad_host(ctx, policy, rewards, n_rewards, m0, S0, reward, pol, seed_fn, seed_user, gc)) return r;
     memcpy(dW, pol.Wbar.data(), sizeof(double) * pol.Wbar.size());
     memcpy(db, pol.bbar.data(), sizeof(double) * pol.bbar.size());
     return PILCO_OK;
@@ -902,7 +833,9 @@ int pilco_rollout_grad_rbf_seeded(pilco_ctx* ctx, const pilco_policy* policy, co
     RbfAdj pol;
     if (!pol.init(bf, policy->state_dim, policy->control_dim, Xp, Yp, lsp, noisep))
         return fail(ctx, PILCO_E_NOT_PD, "rollout_grad_rbf: K + noise I of the policy is singular");
-    if (int r = rollout_grad_impl(ctx, policy, rewards, n_rewards, m0, S0, H, reward, pol, seed_fn, seed_user)) return r;
+    GradCall gc;
+    if (int r = plan_grad(ctx, policy, rewards, n_rewards, H, false, seed_fn != nullptr, nullptr, gc)) return r;
+    if (int r = rollout_grad_host(ctx, policy, rewards, n_rewards, m0, S0, reward, pol, seed_fn, seed_user, gc)) return r;
     pol.finish(dX, dY, dls);
     return PILCO_OK;
 }
@@ -936,59 +869,25 @@ int pilco_rollout_grad_batch_seeded(pilco_ctx* ctx, int B, const pilco_policy* p
     if (int r = rollout_lanes(ctx, B, lane, "rollout_grad_batch")) return r;
     const int E = policies[0].state_dim, U = policies[0].control_dim;
     std::vector<GradCall> gc((size_t)B);
-    int err = PILCO_OK, begun = 0;
-    if (dev_chain_applies(ctx, &policies[0])) {   // every lane's chain on the device: all lanes enqueued before the first wait
-        std::vector<JtapeDev> dv((size_t)B);
-        bool fallback = false;
-        for (int i = 0; i < B && !err; ++i) {
-            const int r = rollout_grad_dev_begin(lane[i], &policies[i], rewards, n_rewards, m0 + (size_t)i * E, S0 + (size_t)i * E * E, H,
-                                                 seed_fn != nullptr, dv[i]);
-            if (r == PILCO_JAC_TOO_LARGE && i == 0) {   // (the same answer for every lane: same model, same horizon)
-                fallback = true;
-                break;
-            }
-            if (r) {
-                err = r;
-                if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
-                break;
-            }
-            ++begun;
-        }
-        if (!fallback) {
-            for (int i = 0; i < begun; ++i) {
-                const int r = rollout_grad_dev_finish(lane[i], dv[i], &policies[i], H, seed_fn, (seed_fn && seed_users) ? seed_users[i] : nullptr,
-                                                      reward + i, dW + (size_t)i * U * E, db + (size_t)i * U);
-                if (r && !err) {
-                    err = r;
-                    if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
-                }
-            }
-            if (err)
-                for (int i = 0; i < B; ++i) (void)hipStreamSynchronize(lane[i]->st);
-            return err;
-        }
-    }
-    for (int i = 0; i < B && !err; ++i, ++begun) {
-        err = rollout_grad_begin(lane[i], &policies[i], rewards, n_rewards, m0 + (size_t)i * E, S0 + (size_t)i * E * E, H, reward + i, gc[i], true);
-        if (err && i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
-        if (err) break;
-    }
-    for (int i = 0; i < begun; ++i) {
+    auto seed_user = [&](int i) { return (seed_fn && seed_users) ? seed_users[i] : nullptr; };
+    // one plan, lane 0's, for every lane (same model, same horizon): with the device chain every lane's chain is enqueued
+    // before the first wait, with a host chain lane i's sweep runs while lanes i + 1.. are still on the device
+    auto begin = [&](int i) {
+        if (int r = plan_grad(lane[i], &policies[i], rewards, n_rewards, H, true, seed_fn != nullptr, i > 0 ? &gc[0].route : nullptr, gc[i])) return r;
+        return grad_forward(lane[i], &policies[i], rewards, n_rewards, m0 + (size_t)i * E, S0 + (size_t)i * E * E, reward + i, true, gc[i]);
+    };
+    auto finish = [&](int i) {
+        if (gc[i].route.chain == GRAD_CHAIN_DEVICE)
+            return grad_device_finish(lane[i], gc[i], seed_fn, seed_user(i), reward + i, dW + (size_t)i * U * E, db + (size_t)i * U);
         LinearAdj pol(E, U, policies[i].W, policies[i].b);
-        const int r = rollout_grad_finish(lane[i], &policies[i], rewards, n_rewards, H, reward + i, pol, seed_fn,
-                                          (seed_fn && seed_users) ? seed_users[i] : nullptr, gc[i]);
-        if (r && !err) {
-            err = r;
-            if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
-        }
+        const int r = rollout_grad_finish(lane[i], &policies[i], rewards, n_rewards, reward + i, pol, seed_fn, seed_user(i), gc[i]);
         if (!r) {
             memcpy(dW + (size_t)i * U * E, pol.Wbar.data(), sizeof(double) * (size_t)U * E);
             memcpy(db + (size_t)i * U, pol.bbar.data(), sizeof(double) * (size_t)U);
         }
-    }
-    if (err)   // a lane that failed after others had begun: nothing may stay in flight behind the caller's back
-        for (int i = 0; i < B; ++i) (void)hipStreamSynchronize(lane[i]->st);
-    return err;
+        return r;
+    };
+    return run_lanes(ctx, lane, true, begin, finish);
 }
 
 int pilco_rollout_grad_batch(pilco_ctx* ctx, int B, const pilco_policy* policies, const pilco_reward_term* rewards, int n_rewards,
@@ -1019,32 +918,23 @@ int pilco_rollout_grad_rbf_batch_seeded(pilco_ctx* ctx, int B, const pilco_polic
     std::vector<double> ones((size_t)U, 1.0);
     std::vector<GradCall> gc((size_t)B);
     std::vector<RbfAdj> pol((size_t)B);
-    int err = PILCO_OK, begun = 0;
-    for (int i = 0; i < B; ++i, ++begun) {
+    auto begin = [&](int i) {
         pilco_ctx* l = lane[i];
-        err = pilco_gp_set_data(l, PILCO_SLOT_POLICY, Xp + i * nX, Yp + i * nY, bf, E, U);
-        if (!err) err = pilco_gp_set_hyp(l, PILCO_SLOT_POLICY, lsp + i * nL, ones.data(), noisep + (size_t)i * U);
-        if (!err) err = pilco_gp_factorize(l, PILCO_SLOT_POLICY);
-        if (!err && !pol[i].init(bf, E, U, Xp + i * nX, Yp + i * nY, lsp + i * nL, noisep + (size_t)i * U))
-            err = fail(l, PILCO_E_NOT_PD, "rollout_grad_rbf_batch: K + noise I of the policy is singular");
-        if (!err) err = rollout_grad_begin(l, &policies[i], rewards, n_rewards, m0 + (size_t)i * E, S0 + (size_t)i * E * E, H, reward + i, gc[i], true);
-        if (err) {
-            if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + l->err;
-            break;
-        }
-    }
-    for (int i = 0; i < begun; ++i) {
-        const int r = rollout_grad_finish(lane[i], &policies[i], rewards, n_rewards, H, reward + i, pol[i], seed_fn,
+        if (int r = pilco_gp_set_data(l, PILCO_SLOT_POLICY, Xp + i * nX, Yp + i * nY, bf, E, U)) return r;
+        if (int r = pilco_gp_set_hyp(l, PILCO_SLOT_POLICY, lsp + i * nL, ones.data(), noisep + (size_t)i * U)) return r;
+        if (int r = pilco_gp_factorize(l, PILCO_SLOT_POLICY)) return r;
+        if (!pol[i].init(bf, E, U, Xp + i * nX, Yp + i * nY, lsp + i * nL, noisep + (size_t)i * U))
+            return fail(l, PILCO_E_NOT_PD, "rollout_grad_rbf_batch: K + noise I of the policy is singular");
+        if (int r = plan_grad(l, &policies[i], rewards, n_rewards, H, false, seed_fn != nullptr, i > 0 ? &gc[0].route : nullptr, gc[i])) return r;
+        return grad_forward(l, &policies[i], rewards, n_rewards, m0 + (size_t)i * E, S0 + (size_t)i * E * E, reward + i, true, gc[i]);
+    };
+    auto finish = [&](int i) {
+        const int r = rollout_grad_finish(lane[i], &policies[i], rewards, n_rewards, reward + i, pol[i], seed_fn,
                                           (seed_fn && seed_users) ? seed_users[i] : nullptr, gc[i]);
-        if (r && !err) {
-            err = r;
-            if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
-        }
         if (!r) pol[i].finish(dX + i * nX, dY + i * nY, dls + i * nL);
-    }
-    if (err)
-        for (int i = 0; i < B; ++i) (void)hipStreamSynchronize(lane[i]->st);
-    return err;
+        return r;
+    };
+    return run_lanes(ctx, lane, true, begin, finish);
 }
 int pilco_rollout_grad_rbf_batch(pilco_ctx* ctx, int B, const pilco_policy* policies, const pilco_reward_term* rewards, int n_rewards,
                                  const double* m0, const double* S0, int H, const double* Xp, const double* Yp, const double* lsp,

@@ -124,7 +124,7 @@ struct GlueArgs {
                      // workgroup reads s1 while the writer workgroup stores the next one)
     double* reward;  // [1]
     double* traj;    // [(H+1)][E + E*E] or nullptr
-    double* tape;    // [H][D + D*D + E*D + E + E*E + D*E] joint (m, s, s1) and GP outputs (M, S, V) of every step, or nullptr
+    double* tape;    // [H][tape_rec(D, E).size] (grad_layout.h): joint (m, s, s1) and GP outputs (M, S, V) of every step, or nullptr
     int step;
     int dbg_off;     // developer aid: slot offset of this launch's phase stamps (0 = default)
     // RbfController evaluated INSIDE the link (glue_device.h: rbf_policy_inline) instead of by an operand + pair launch of its
@@ -237,19 +237,19 @@ struct RevArgs {
     int E, U, D, H, P;      // P = E (E + 1) / 2: the pairs of the WHOLE model
     // Jacobian records: step t starts at jrec + t * gstep; pair kk of the dealing order ((0,0) .. (E-1,E-1), (1,0), (2,0), (2,1), ..)
     // lives in rank kk % W's block as its pair kk / W: + (kk % W) * gblk + (kk / W) * recp; the E output records at + out_off
-    // (rank 0's).  One rank: W = 1, gstep = mm_jac_rec_size, out_off = P * recp.
+    // (rank 0's): jac_gather (grad_layout.h).  One rank: W = 1, gstep = mm_jac_rec_size, out_off = P * recp.
     const double* jrec;
     int W;
     long gblk, gstep, out_off;
     const double* traj;     // [H + 1][E + E*E]
-    const double* tape;     // [H][TS]: m_j | s_j | s1 (E,D) | M (E) | S (E,E) | V (D,E)
+    const double* tape;     // [H][TS]: the tape records (tape_rec, grad_layout.h)
     long TS;
     const double* loc;      // [H][rev_loc_doubles]  (k_rev_local: reward gradients, controller / squash forward quantities)
     const double* seeds;    // [H + 1][E + E*E] cotangent seeds of the caller's objective, or nullptr
     const double* Wp;       // LinearController W (U,E)
     const double* reward_dev;   // the rollout's reward on the device: handed out with the gradient (out[..]) instead of a copy of its own in front of the finish
     double* amat;           // [H][rev_mat_doubles]: every step's reverse map [A; B] by columns | r | flags  (k_rev_step -> k_rev_chain)
-    double* out;            // [U*E + U + 1 + E + E(E+1)/2 + 1]: dW | db | status (0 fine) | d / d (m_0, S_0 packed) | reward   (device-visible)
+    double* out;            // [rev_out(E, U).size] (grad_layout.h): dW | db | status (0 fine) | d / d (m_0, S_0 packed) | reward   (device-visible)
 };
 bool rev_chain_supported(int E, int U, int D);
 size_t rev_step_lds_bytes(int E, int U, int D);   // dynamic LDS of one k_rev_step workgroup

@@ -13,6 +13,7 @@
 //   k_rev_chain   ONE workgroup walks t = H-1 .. 0: a matrix-vector product per step, gradient accumulators in registers.
 // Fixed summation orders throughout: the gradient is bitwise repeatable, and identical on every rank of a sharded model
 // (every rank runs the same chain over the same all-gathered records).
+#include "grad_layout.h"
 #include "rev_local.h"
 
 namespace pilco {
@@ -28,17 +29,7 @@ namespace pilco {
 // 77 x 65 map x -> (mbar_joint | sbar_joint), pushes the 65 basis cotangents through joint Gaussian, squash and controller
 // (pilco.py:141-144, controllers.py:13-58) and leaves [A_t; B_t] (76 x 65, stored by columns) and r_t; what remains
 // sequential is one 40 kB matrix-vector product per step with two barriers (k_rev_chain).
-struct RevDims {
-    int E, U, D, P, NX, NP, NR, NOUT, NT2, nI, recp, reco;
-};
-__host__ __device__ inline RevDims rev_dims(int E, int U, int D) {
-    RevDims d;
-    d.E = E; d.U = U; d.D = D; d.P = E * (E + 1) / 2;
-    d.NX = E + d.P; d.NP = U * E + U; d.NR = d.NX + d.NP;
-    d.NT2 = D * (D + 1) / 2; d.NOUT = D + d.NT2; d.nI = D * D;
-    d.recp = 1 + d.NOUT; d.reco = d.NOUT + d.nI + D * d.NT2;
-    return d;
-}
+// (the dimensions NX, NP, NR, .. and the records' recp / reco: RevDims, grad_layout.h)
 constexpr int REVS_SPLIT = 4;   // workgroups per step of k_rev_step (column ranges of [A; B]); a flag each
 size_t rev_mat_doubles(int E, int U, int D) {   // per step: [A; B] by columns | r | flags
     const RevDims d = rev_dims(E, U, D);

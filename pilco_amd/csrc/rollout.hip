@@ -2,7 +2,6 @@
 // and replay, and the policy / reward evaluation entry points.
 #include "ctx.h"
 #include "reward_factor.h"
-#include <chrono>
 
 namespace {
 
@@ -240,21 +239,6 @@ static int plan_route(pilco_ctx* ctx, RolloutPlan& plan, int H, bool timed) {
     w[ROUTE_H] = H;
     w[ROUTE_NPAD] = s.npad;
     return PILCO_OK;
-}
-
-// Jacobian tape: the sums, moments and records of steps [t0, t1) in two launches behind the chain (rollout_jtape enqueues
-// them per chunk of steps, last steps first, each followed by its download: the host's reverse sweep works on one chunk
-// while the device finishes the next)
-static void jac_finish_range(pilco_ctx* ctx, const RolloutPlan& plan, int t0, int t1, const RevLocalArgs* rl = nullptr) {
-    Slot& s = ctx->slot[0];
-    hipStream_t st = ctx->st;
-    const int D = plan.D, E = plan.E, P = s.wk.PL;
-    const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
-    const size_t o = (size_t)t0;
-    launch_mm_jac_finish(st, model_of(s), s.wk, t1 - t0, s.jac_rowmom.p + o * mm_jac_rowmom_size(s.npad, P),
-                         s.jac_cpart.p + o * mm_jac_cpart_size(s.npad, P, s.wk.EL), s.jac_head.p + o * mm_jac_head_size(D, E, P),
-                         s.jac_part.p + o * mm_jac_part_size(D, E, P, s.npad), plan.g.tape + o * TS, TS, plan.jrec + o * plan.jstride,
-                         s.wk.NCH * plan.route.ncs, rl);   // (the small step's chunks per pair, or 0)
 }
 
 // The reward of a state (pilco.py:133) rides in a spare workgroup of a head or prep launch: of the state the link holds in
@@ -649,6 +633,15 @@ static int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H, Upload&& upload
     return PILCO_OK;
 }
 
+int rollout_run(pilco_ctx* ctx, RolloutPlan& plan, int H, const double* m0, const double* S0) {
+    auto upload = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(plan.st[0], m0, sizeof(double) * plan.E, hipMemcpyHostToDevice, ctx->st));
+        HIPCHK(hipMemcpyAsync(plan.st[0] + plan.E, S0, sizeof(double) * plan.E * plan.E, hipMemcpyHostToDevice, ctx->st));
+        return PILCO_OK;
+    };
+    return run_rollout(ctx, plan, H, upload);
+}
+
 // pilco_rollout in two halves, so that several rollouts (the lanes of pilco_rollout_batch) can be in flight at once:
 // rollout_begin enqueues everything -- upload of (m0, S0), the rollout, the downloads into pinned memory -- and returns;
 // rollout_end waits for the stream and hands the results out.
@@ -792,29 +785,14 @@ int pilco_rollout_batch(pilco_ctx* ctx, int B, const pilco_policy* policies, con
     const Slot& s = ctx->slot[0];
     if (!s.factor_valid) return fail(ctx, PILCO_E_STATE, "rollout_batch: dynamics model has no current factorisation");
     const int E = s.E;
-    const size_t nst = (size_t)E + (size_t)E * E;
     std::vector<RolloutCall> rc((size_t)B);
     std::vector<pilco_ctx*> lane;
     LanesGuard lanes_guard{ctx};
     if (int r = rollout_lanes(ctx, B, lane, "rollout_batch")) return r;
-    int rc_err = PILCO_OK;
-    int begun = 0;
-    for (int i = 0; i < B; ++i, ++begun) {
-        rc_err = rollout_begin(lane[i], &policies[i], rewards, n_rewards, m0 + (size_t)i * E, S0 + (size_t)i * E * E, H, nullptr, rc[i]);
-        if (rc_err) {
-            if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
-            break;
-        }
-    }
-    for (int i = 0; i < begun; ++i) {
-        const int r = rollout_end(lane[i], rc[i], mH + (size_t)i * E, SH + (size_t)i * E * E, reward + i);
-        if (r && !rc_err) {
-            rc_err = r;
-            if (i > 0) ctx->err = "lane " + std::to_string(i) + ": " + lane[i]->err;
-        }
-    }
-    (void)nst;
-    return rc_err;
+    return run_lanes(
+        ctx, lane, false,
+        [&](int i) { return rollout_begin(lane[i], &policies[i], rewards, n_rewards, m0 + (size_t)i * E, S0 + (size_t)i * E * E, H, nullptr, rc[i]); },
+        [&](int i) { return rollout_end(lane[i], rc[i], mH + (size_t)i * E, SH + (size_t)i * E * E, reward + i); });
 }
 
 int pilco_propagate(pilco_ctx* ctx, const pilco_policy* policy, const double* m_x, const double* s_x, double* M_x, double* S_x) {
@@ -996,7 +974,7 @@ int pilco_rollout_timed(pilco_ctx* ctx, const pilco_policy* policy, const pilco_
 }
 
 // pilco_rollout that also records, for every step t < H, the joint Gaussian (m, s, s1) handed to
-// the dynamics GP and its outputs (M, S, V): tape [H][D + D*D + E*D + E + E*E + D*E].  The reverse
+// the dynamics GP and its outputs (M, S, V): tape [H][tape_rec(D, E).size] (grad_layout.h).  The reverse
 // sweep of the policy gradient replays these records (pilco_amd/adjoint.py).
 int pilco_rollout_tape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
                        const double* m0, const double* S0, int H, double* mH, double* SH, double* reward, double* traj,
@@ -1006,16 +984,11 @@ int pilco_rollout_tape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_r
     HIPCHK(hipSetDevice(ctx->device));
     RolloutPlan plan;
     if (int r = setup_rollout(ctx, policy, rewards, n_rewards, H, traj != nullptr, plan)) return r;
-    const int E = plan.E, D = plan.D;
-    const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
+    const int E = plan.E;
+    const size_t TS = tape_rec(plan.D, E).size;
     ENSURE(ctx->tape, std::max<size_t>(1, (size_t)H * TS));
     plan.g.tape = ctx->tape.p;
-    auto upload = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(plan.st[0], m0, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
-        HIPCHK(hipMemcpyAsync(plan.st[0] + E, S0, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
-        return PILCO_OK;
-    };
-    if (int r = run_rollout(ctx, plan, H, upload)) return r;   // replayed as a hipGraph like pilco_rollout (the tape pointer is part of the graph key)
+    if (int r = rollout_run(ctx, plan, H, m0, S0)) return r;   // replayed as a hipGraph like pilco_rollout (the tape pointer is part of the graph key)
     HIPCHK(hipMemcpyAsync(mH, plan.st[H & 1], sizeof(double) * E, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(SH, plan.st[H & 1] + E, sizeof(double) * E * E, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipMemcpyAsync(reward, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
@@ -1027,282 +1000,6 @@ int pilco_rollout_tape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_r
 }
 
 }  // extern "C"
-
-// Value-and-gradient rollout, forward half: pilco_rollout_tape with every dynamics step run as the reverse sweep
-// (launch_mm_jac), so that the step's value and its Jacobian records come out of ONE O(N^2) pass; trajectory, tape and
-// records land in pinned host memory for the host-side reverse sweep (grad.hip).  Single rank; D <= 14 (wider inputs: PILCO_JAC_TOO_LARGE, the caller
-// falls back to the plain tape + per-step device adjoint, which has the forward path's D <= 32).
-int rollout_jtape(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* m0,
-                  const double* S0, int H, double* reward, const double** traj, const double** tape, const double** jrec, size_t* jstride,
-                  const double** reward_later, JtapeDev* dev) {
-    HIPCHK(hipSetDevice(ctx->device));
-    // Several ranks (round 3): every rank sweeps ITS pairs (k_mm_bwd_pair is per-pair independent; the mean-part records of
-    // all E outputs are cheap and computed everywhere), the per-step exchange of the forward chain is the sharded
-    // rollout's own (RCCL all-gather, or host-mediated inside pilco_rollout_grad_group), and after the batched finish the
-    // per-pair records are all-gathered ONCE -- records, not sums: the host sweep below adds them in the single-rank order.
-    const int W = ctx->nranks;
-    const bool sharded = (W != 1 || ctx->comm);
-    if (sharded && !ctx->comm && !ctx->group)
-        return fail(ctx, PILCO_E_STATE, "rollout_grad: a sharded context needs a communicator (pilco_comm_init) or pilco_rollout_grad_group");
-    RolloutPlan plan;
-    if (int r = setup_rollout(ctx, policy, rewards, n_rewards, H, true, plan)) return r;
-    Slot& s = ctx->slot[0];
-    const int E = plan.E, D = plan.D, P = s.wk.PL, npad = s.npad;
-    if (D > 14) return PILCO_JAC_TOO_LARGE;   // third-moment records and their LDS working set are sized for D <= 14
-    const size_t TS = (size_t)D + D * D + (size_t)E * D + E + (size_t)E * E + (size_t)D * E;
-    const size_t JS = mm_jac_rec_size(D, E, P), NTJ = (size_t)(H + 1) * (E + (size_t)E * E);
-    // every step keeps its own sweep output until the batched finish (nothing on the chain waits for a buffer): at C2u
-    // 29 MB per step -- HBM is 288 GB; a rollout that would need more than PILCO_JAC_GB (default 32) falls back
-    const size_t Hn = (size_t)std::max(H, 1);
-    const int ELc = s.wk.EL;   // owned outputs = diagonal pairs held here (E on one rank)
-    const size_t per_step = mm_jac_rowmom_size(npad, P) + mm_jac_cpart_size(npad, P, ELc) + mm_jac_head_size(D, E, P) + mm_jac_part_size(D, E, P, npad);
-    double cap_gb = 32.0;
-    if (const char* ev = getenv("PILCO_JAC_GB")) cap_gb = atof(ev);
-    if ((double)per_step * 8.0 * (double)Hn > cap_gb * 1e9) return PILCO_JAC_TOO_LARGE;
-    ENSURE(s.jac_rowmom, Hn * mm_jac_rowmom_size(npad, P));
-    ENSURE(s.jac_cpart, Hn * mm_jac_cpart_size(npad, P, ELc));
-    ENSURE(s.jac_head, Hn * mm_jac_head_size(D, E, P));
-    ENSURE(s.jac_part, Hn * mm_jac_part_size(D, E, P, npad));
-    ENSURE(s.jac_np, (size_t)2 * std::max(P, 1) * mm_jac_nt(npad, s.wk.P));
-    ENSURE(ctx->tape, std::max<size_t>(1, (size_t)H * TS));
-    ENSURE(ctx->jrec, std::max<size_t>(1, (size_t)H * JS));
-    // sharded: the host sweep reads GLOBAL records [P_all pair records | E output records] per step, assembled on the host
-    // from every rank's pair records (all-gathered) and this rank's own output records
-    const int NT2 = D * (D + 1) / 2, recp = 1 + D + NT2, Pall = E * (E + 1) / 2, PLcap = (Pall + W - 1) / W;
-    const size_t reco = (size_t)D + NT2 + (size_t)D * D + (size_t)D * NT2;
-    const size_t JSg = sharded ? (size_t)Pall * recp + (size_t)E * reco : JS;
-    // one rank's block: per step its pair records (padded to PLcap) and the E output records (every rank WITH pairs computes
-    // them all; a rank without pairs runs no sweep at all, so the readers take them from rank 0, which always has pairs)
-    const size_t gstep = (size_t)PLcap * recp + (size_t)E * reco;
-    const size_t gblk = (size_t)std::max(H, 1) * gstep;
-    const size_t SEd = (size_t)E + (size_t)E * E;
-    if (dev) {
-        dev->n_seeds = (size_t)(H + 1) * SEd;
-        dev->n_out = (size_t)plan.U * E + plan.U + 1 + SEd + 2;
-    }
-    const size_t need = dev ? NTJ + 8 + dev->n_seeds + dev->n_out + 8
-                            : NTJ + (size_t)H * TS + (size_t)H * JSg + 8 + (sharded ? (size_t)W * gblk : 0);
-    if (ctx->jpin_cap < need) {
-        if (ctx->jpin) (void)hipHostFree(ctx->jpin);
-        ctx->jpin = nullptr;
-        ctx->jpin_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&ctx->jpin, sizeof(double) * need, hipHostMallocDefault));
-        ctx->jpin_cap = need;
-    }
-    double* h_traj = ctx->jpin;
-    double* h_tape = h_traj + NTJ;
-    double* h_jrec = h_tape + (size_t)H * TS;
-    plan.g.tape = ctx->tape.p;
-    // one rank: k_mm_jac_fin writes the records straight into the pinned host buffer (device-visible): their 4.3 MB cross
-    // PCIe while the kernel runs instead of as four copies that hold the stream between the chunks of the finish
-    const bool jdirect = !dev && !sharded && getenv("PILCO_JAC_COPY") == nullptr;
-    plan.jrec = jdirect ? h_jrec : ctx->jrec.p;
-    plan.jstride = JS;
-    double* h_misc = dev ? h_traj + NTJ : h_jrec + (size_t)H * JSg;
-    double* h_all = h_misc + 8;                          // sharded: [W][H][PLcap * recp | E * reco]
-    auto upload = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(plan.st[0], m0, sizeof(double) * E, hipMemcpyHostToDevice, ctx->st));
-        HIPCHK(hipMemcpyAsync(plan.st[0] + E, S0, sizeof(double) * E * E, hipMemcpyHostToDevice, ctx->st));
-        return PILCO_OK;
-    };
-    if (int r = run_rollout(ctx, plan, H, upload)) return r;   // (plan.route: the steps' layout the finish reads)
-    if (!dev) HIPCHK(hipMemcpyAsync(h_misc, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
-    if (dev) {
-        // ---- the reverse chain on the device (rev.hip): nothing but the reward, the gradient -- and, for a caller with
-        // cotangent seeds, the trajectory -- crosses to the host
-        if (!ctx->jwait_ev[0]) HIPCHK(hipEventCreateWithFlags(&ctx->jwait_ev[0], hipEventDisableTiming));
-        if (dev->seeds) {
-            HIPCHK(hipMemcpyAsync(h_traj, ctx->traj.p, sizeof(double) * NTJ, hipMemcpyDeviceToHost, ctx->st));
-            HIPCHK(hipEventRecord(ctx->jwait_ev[0], ctx->st));   // the host turns the trajectory into seeds while the finish runs
-        }
-        RevArgs& ra = dev->ra;
-        ra = RevArgs{};
-        ra.E = E; ra.U = plan.U; ra.D = D; ra.H = H; ra.P = Pall;
-        ra.W = 1; ra.gblk = 0; ra.gstep = (long)JS; ra.out_off = (long)P * recp;
-        ra.jrec = ctx->jrec.p;
-        ENSURE(ctx->revloc, std::max<size_t>(1, (size_t)H * rev_loc_doubles(E, plan.U)));
-        const RevLocalArgs rl = rev_local_args(plan.g.n_rewards, plan.g.rw, E, plan.U, ctx->traj.p, plan.g.W, plan.g.b, plan.g.maxact, ctx->revloc.p);
-        if (H > 0) {
-            jac_finish_range(ctx, plan, 0, H, &rl);   // (the trajectory-only quantities of the chain ride in its last launch)
-            if (sharded) {   // every rank's pair records, all-gathered ONCE; the chain reads them where they land
-                ENSURE(ctx->jgath, (size_t)(W + 1) * gblk);
-                double* own = ctx->jgath.p + (size_t)W * gblk;
-                HIPCHK(hipMemsetAsync(own, 0, sizeof(double) * gblk, ctx->st));
-                if (P > 0) {
-                    HIPCHK(hipMemcpy2DAsync(own, sizeof(double) * gstep, ctx->jrec.p, sizeof(double) * JS, sizeof(double) * P * recp, (size_t)H,
-                                            hipMemcpyDeviceToDevice, ctx->st));
-                    HIPCHK(hipMemcpy2DAsync(own + (size_t)PLcap * recp, sizeof(double) * gstep, ctx->jrec.p + (size_t)P * recp, sizeof(double) * JS,
-                                            sizeof(double) * E * reco, (size_t)H, hipMemcpyDeviceToDevice, ctx->st));
-                }
-                if (ctx->comm) {
-                    ncclResult_t r = ncclAllGather(own, ctx->jgath.p, gblk, ncclDouble, ctx->comm, ctx->st);
-                    if (r != ncclSuccess) return fail(ctx, PILCO_E_RCCL, std::string("ncclAllGather(jacobian records): ") + ncclGetErrorString(r));
-                } else {   // contexts of one process (pilco_rollout_grad_group): take the peers' blocks between two host barriers
-                    HIPCHK(hipStreamSynchronize(ctx->st));
-                    std::shared_ptr<PeerGroup> grp = ctx->group;
-                    if (!grp->arrive_and_wait()) return fail(ctx, PILCO_E_STATE, "rollout_grad: another rank of the group failed");
-                    // (on THIS context's stream: a device-to-device hipMemcpy is ordered on the null stream only and need not have
-                    // finished when it returns -- the chain below, on a non-blocking stream, read blocks that were still being
-                    // copied once in ten runs; the peers may reuse their blocks after the second barrier, so the copies are
-                    // waited for in front of it)
-                    for (int j = 0; j < W; ++j) {
-                        pilco_ctx* pj = grp->ctxs[j];
-                        HIPCHK(hipMemcpyAsync(ctx->jgath.p + (size_t)j * gblk, pj->jgath.p + (size_t)W * gblk, sizeof(double) * gblk, hipMemcpyDeviceToDevice,
-                                              ctx->st));
-                    }
-                    HIPCHK(hipStreamSynchronize(ctx->st));
-                    if (!grp->arrive_and_wait()) return fail(ctx, PILCO_E_STATE, "rollout_grad: another rank of the group failed");
-                }
-                ra.jrec = ctx->jgath.p;
-                ra.W = W; ra.gblk = (long)gblk; ra.gstep = (long)gstep; ra.out_off = (long)PLcap * recp;
-            }
-        }
-        ra.traj = ctx->traj.p;
-        ra.tape = ctx->tape.p;
-        ra.TS = (long)TS;
-        ra.loc = ctx->revloc.p;
-        ENSURE(ctx->revmat, std::max<size_t>(1, (size_t)H * rev_mat_doubles(E, plan.U, D)));
-        ra.amat = ctx->revmat.p;
-        ra.seeds = nullptr;
-        ra.reward_dev = plan.g.reward;
-        ra.Wp = plan.g.W;
-        dev->h_seeds = h_misc + 8;
-        double* h_out = dev->h_seeds + dev->n_seeds;
-        ra.out = h_out;
-        dev->h_out = h_out;
-        dev->h_traj = h_traj;
-        dev->h_reward = h_out + ((size_t)plan.U * E + plan.U) + 1 + (size_t)(E + Pall);   // (written by the chain kernel)
-        if (!dev->seeds) launch_rev_chain(ctx->st, ra);
-        HIPCHK(hipGetLastError());
-        return PILCO_OK;
-    }
-    HIPCHK(hipMemcpyAsync(h_traj, ctx->traj.p, sizeof(double) * NTJ, hipMemcpyDeviceToHost, ctx->st));
-    // the records come down in chunks, LAST steps first, an event behind each: the host's reverse sweep starts on the
-    // last steps while the earlier ones are still on their way (rollout_jtape_wait)
-    ctx->jwait_from = H;
-    ctx->jwait_next = 0;
-    ctx->jwait_n = 0;
-    if (H > 0 && sharded) {
-        jac_finish_range(ctx, plan, 0, H);
-        HIPCHK(hipMemcpyAsync(h_tape, ctx->tape.p, sizeof(double) * (size_t)H * TS, hipMemcpyDeviceToHost, ctx->st));
-        ENSURE(ctx->jgath, (size_t)(W + 1) * gblk);
-        double* own = ctx->jgath.p + (size_t)W * gblk;
-        HIPCHK(hipMemsetAsync(own, 0, sizeof(double) * gblk, ctx->st));
-        if (P > 0) {   // this rank's records of every step, compacted: [H][PLcap pair records | E output records]
-            HIPCHK(hipMemcpy2DAsync(own, sizeof(double) * gstep, ctx->jrec.p, sizeof(double) * JS, sizeof(double) * P * recp, (size_t)H,
-                                    hipMemcpyDeviceToDevice, ctx->st));
-            HIPCHK(hipMemcpy2DAsync(own + (size_t)PLcap * recp, sizeof(double) * gstep, ctx->jrec.p + (size_t)P * recp, sizeof(double) * JS,
-                                    sizeof(double) * E * reco, (size_t)H, hipMemcpyDeviceToDevice, ctx->st));
-        }
-        if (ctx->comm) {
-            ncclResult_t r = ncclAllGather(own, ctx->jgath.p, gblk, ncclDouble, ctx->comm, ctx->st);
-            if (r != ncclSuccess) return fail(ctx, PILCO_E_RCCL, std::string("ncclAllGather(jacobian records): ") + ncclGetErrorString(r));
-            HIPCHK(hipMemcpyAsync(h_all, ctx->jgath.p, sizeof(double) * (size_t)W * gblk, hipMemcpyDeviceToHost, ctx->st));
-            HIPCHK(hipStreamSynchronize(ctx->st));
-        } else {   // contexts of one process (pilco_rollout_grad_group): read the peers' blocks between two host barriers
-            HIPCHK(hipStreamSynchronize(ctx->st));
-            std::shared_ptr<PeerGroup> grp = ctx->group;
-            if (!grp->arrive_and_wait()) return fail(ctx, PILCO_E_STATE, "rollout_grad: another rank of the group failed");
-            for (int j = 0; j < W; ++j) {
-                pilco_ctx* pj = grp->ctxs[j];
-                HIPCHK(hipMemcpy(h_all + (size_t)j * gblk, pj->jgath.p + (size_t)W * gblk, sizeof(double) * gblk, hipMemcpyDeviceToHost));
-            }
-            if (!grp->arrive_and_wait()) return fail(ctx, PILCO_E_STATE, "rollout_grad: another rank of the group failed");
-        }
-        HIPCHK(hipGetLastError());
-        for (int t = 0; t < H; ++t) {   // global record of step t: pair kk of the dealing order lives on rank kk % W as its pair kk / W
-            double* dst = h_jrec + (size_t)t * JSg;
-            for (int kk = 0; kk < Pall; ++kk)
-                memcpy(dst + (size_t)kk * recp, h_all + (size_t)(kk % W) * gblk + (size_t)t * gstep + (size_t)(kk / W) * recp, sizeof(double) * recp);
-            memcpy(dst + (size_t)Pall * recp, h_all + (size_t)t * gstep + (size_t)PLcap * recp, sizeof(double) * E * reco);   // rank 0's
-        }
-        ctx->jwait_n = 0;
-        ctx->jwait_from = 0;
-    } else if (H > 0) {
-        HIPCHK(hipMemcpyAsync(h_tape, ctx->tape.p, sizeof(double) * (size_t)H * TS, hipMemcpyDeviceToHost, ctx->st));
-        // chunks in the order the reverse sweep consumes them, SHRINKING towards step 0.  Measured at C2u (gpurun_out/r03/
-        // chunks*.log): the device finishes a step's records in ~11 us, the host sweeps one in ~9 us, and every chunk costs
-        // both sides a fixed ~40-60 us (two launches, a copy, an event wait) -- four chunks of 16/12/8/4 fortieths: 6.03 ->
-        // 5.97 ms; six chunks (8,8,8,8,4,4): 6.14 ms; finishing the early chunks on a second stream WHILE the chain runs:
-        // 6.09 ms with one fork, 7.4 ms with three (the chain's kernels lose what the finish gains)
-        static const int parts[4] = {16, 12, 8, 4};   // fortieths of H
-        const int nch = std::min(H, 4);
-        int t1 = H, used = 0;
-        for (int k = 0; k < nch; ++k) {
-            used += parts[k];
-            const int t0 = (k == nch - 1) ? 0 : std::min(t1 - 1, std::max(0, H - (int)((long)used * H / 40)));   // steps [t0, t1), never empty
-            jac_finish_range(ctx, plan, t0, t1);
-            if (!jdirect)
-                HIPCHK(hipMemcpyAsync(h_jrec + (size_t)t0 * JS, ctx->jrec.p + (size_t)t0 * JS, sizeof(double) * (size_t)(t1 - t0) * JS,
-                                      hipMemcpyDeviceToHost, ctx->st));
-            if (!ctx->jwait_ev[k]) HIPCHK(hipEventCreateWithFlags(&ctx->jwait_ev[k], hipEventDisableTiming));
-            HIPCHK(hipEventRecord(ctx->jwait_ev[k], ctx->st));
-            ctx->jwait_t0[k] = t0;
-            t1 = t0;
-        }
-        ctx->jwait_n = nch;
-        if (reward_later) {   // a lane of a batch: everything is enqueued, the caller waits when it gets to this lane
-            *reward_later = h_misc;
-            *traj = h_traj;
-            *tape = h_tape;
-            *jrec = h_jrec;
-            *jstride = JSg;
-            return PILCO_OK;
-        }
-        if (int r = rollout_jtape_wait(ctx, H - 1)) return r;   // reward, trajectory, tape and the last chunk are on the host
-    } else {
-        HIPCHK(hipStreamSynchronize(ctx->st));
-    }
-    HIPCHK(hipGetLastError());
-    *reward = h_misc[0];
-    *traj = h_traj;
-    *tape = h_tape;
-    *jrec = h_jrec;
-    *jstride = JSg;
-    return PILCO_OK;
-}
-
-// Device reverse chain, second half: with seeds, wait for the trajectory, let the caller turn it into cotangent seeds, upload
-// them and launch the chain; then wait for the gradient.  dev.h_out / dev.h_reward are valid on PILCO_OK.
-int rollout_jtape_dev_finish(pilco_ctx* ctx, JtapeDev& dev, int H, int E, jtape_seed_fn seed_fn, void* seed_user) {
-    HIPCHK(hipSetDevice(ctx->device));
-    if (dev.seeds) {
-        HIPCHK(hipEventSynchronize(ctx->jwait_ev[0]));
-        std::fill(dev.h_seeds, dev.h_seeds + dev.n_seeds, 0.0);
-        seed_fn(seed_user, H, E, dev.h_traj, dev.h_seeds);
-        for (size_t q = 0; q < dev.n_seeds; ++q)
-            if (!std::isfinite(dev.h_seeds[q])) {
-                (void)hipStreamSynchronize(ctx->st);
-                return fail(ctx, PILCO_E_SHAPE, "rollout_grad: the seed callback returned a non-finite cotangent");
-            }
-        ENSURE(ctx->revseeds, dev.n_seeds);
-        HIPCHK(hipMemcpyAsync(ctx->revseeds.p, dev.h_seeds, sizeof(double) * dev.n_seeds, hipMemcpyHostToDevice, ctx->st));
-        dev.ra.seeds = ctx->revseeds.p;
-        launch_rev_chain(ctx->st, dev.ra);
-    }
-    HIPCHK(hipStreamSynchronize(ctx->st));
-    HIPCHK(hipGetLastError());
-    const double status = dev.h_out[(size_t)dev.ra.U * dev.ra.E + dev.ra.U];
-    if (status == 1.0) return fail(ctx, PILCO_E_NOT_PD, "rollout_grad: singular s + Lambda^2 or I + Lambda s");
-    if (status != 0.0) return fail(ctx, PILCO_E_NOT_PD, "rollout_grad: singular I + S W in the reward");
-    return PILCO_OK;
-}
-
-// Block until the records of step t (and everything enqueued before them) are on the host.
-int rollout_jtape_wait(pilco_ctx* ctx, int t) {
-    while (t < ctx->jwait_from && ctx->jwait_next < ctx->jwait_n) {
-        const int k = ctx->jwait_next++;
-        static const bool timing = getenv("PILCO_GRAD_TIMING") != nullptr;   // developer aid: how long the host waited for chunk k
-        const auto w0 = std::chrono::steady_clock::now();
-        HIPCHK(hipEventSynchronize(ctx->jwait_ev[k]));
-        if (timing)
-            fprintf(stderr, "[pilco grad] chunk %d (steps >= %d): waited %.3f ms (asked for step %d)\n", k, ctx->jwait_t0[k],
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count(), t);
-        ctx->jwait_from = ctx->jwait_t0[k];
-    }
-    return PILCO_OK;
-}
-
 
 // test aid (pilco_debug_geometry): the step geometry of the dynamics slot's current workspace
 int pilco_debug_geometry(pilco_ctx* ctx, int* out, int n) {

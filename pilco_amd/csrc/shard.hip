@@ -88,6 +88,35 @@ int peer_detach(pilco_ctx* ctx) {
     return PILCO_OK;
 }
 
+// Run one call on every context of a group of n contexts of THIS process (rank i = ctxs[i], any devices), each on a host
+// thread of its own, with the group's host barrier (PeerGroup) attached for the duration: call(i) is context i's call.  A
+// rank that fails releases the others; the first failing rank's error is the group's, labelled with its rank on ctxs[0].
+template <class Call>
+static int run_group(pilco_ctx** ctxs, int n, const char* who, Call&& call) {
+    pilco_ctx* c0 = ctxs[0];
+    for (int i = 0; i < n; ++i)
+        if (!ctxs[i] || ctxs[i]->nranks != n || ctxs[i]->rank != i || ctxs[i]->comm)
+            return fail(c0, PILCO_E_STATE, std::string(who) + ": context i must be shard_set(i, n) and have no communicator");
+    auto grp = std::make_shared<PeerGroup>();
+    grp->ctxs.assign(ctxs, ctxs + n);
+    for (int i = 0; i < n; ++i) ctxs[i]->group = grp;
+    std::vector<int> rc(n, PILCO_OK);
+    std::vector<std::thread> th;
+    for (int i = 0; i < n; ++i)
+        th.emplace_back([&, i] {
+            rc[i] = call(i);
+            if (rc[i] != PILCO_OK) grp->fail_all();
+        });
+    for (auto& t : th) t.join();
+    for (int i = 0; i < n; ++i) ctxs[i]->group.reset();
+    for (int i = 0; i < n; ++i)
+        if (rc[i] != PILCO_OK) {
+            if (i != 0) c0->err = "rank " + std::to_string(i) + ": " + ctxs[i]->err;
+            return rc[i];
+        }
+    return PILCO_OK;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------ multi-GPU
@@ -297,42 +326,23 @@ int pilco_gp_beta_import(pilco_ctx* ctx, int slot, const double* all_rows) {
     return PILCO_OK;
 }
 
-// One sharded rollout over n contexts of THIS process (rank i = ctxs[i], any devices): every context runs its own
-// pilco_rollout on a host thread; the per-step exchange is done by peer copies between host barriers.  It drives exactly
-// the launch sequence the RCCL path runs (PACK launch, exchange, tail launch) with the collective swapped for copies,
-// so the sharded rollout can be validated on a single GPU.  Outputs: rank 0's; *mismatch = 1 if any other rank ended
-// with a different bit pattern.
+// One sharded rollout over n contexts of THIS process: every context runs its own pilco_rollout; the per-step exchange is
+// done by peer copies between host barriers.  It drives exactly the launch sequence the RCCL path runs (PACK launch,
+// exchange, tail launch) with the collective swapped for copies, so the sharded rollout can be validated on a single GPU.
+// Outputs: rank 0's; *mismatch = 1 if any other rank ended with a different bit pattern.
 int pilco_rollout_group(pilco_ctx** ctxs, int n, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
                         const double* m0, const double* S0, int H, double* mH, double* SH, double* reward, double* traj,
                         int* mismatch) {
     if (!ctxs || n <= 0 || !ctxs[0]) return PILCO_E_SHAPE;
-    pilco_ctx* c0 = ctxs[0];
-    if (!policy || !mH || !SH || !reward) return fail(c0, PILCO_E_SHAPE, "rollout_group: null pointer");
-    for (int i = 0; i < n; ++i)
-        if (!ctxs[i] || ctxs[i]->nranks != n || ctxs[i]->rank != i || ctxs[i]->comm)
-            return fail(c0, PILCO_E_STATE, "rollout_group: context i must be shard_set(i, n) and have no communicator");
+    if (!policy || !mH || !SH || !reward) return fail(ctxs[0], PILCO_E_SHAPE, "rollout_group: null pointer");
     const int E = policy->state_dim;
-    auto grp = std::make_shared<PeerGroup>();
-    grp->ctxs.assign(ctxs, ctxs + n);
-    for (int i = 0; i < n; ++i) ctxs[i]->group = grp;
     const size_t nt = traj ? (size_t)(H + 1) * (E + (size_t)E * E) : 0;
     std::vector<std::vector<double>> om(n, std::vector<double>(E)), os(n, std::vector<double>((size_t)E * E)), orw(n, std::vector<double>(1)),
         otr(n, std::vector<double>(nt));
-    std::vector<int> rc(n, PILCO_OK);
-    std::vector<std::thread> th;
-    for (int i = 0; i < n; ++i)
-        th.emplace_back([&, i] {
-            rc[i] = pilco_rollout(ctxs[i], policy, rewards, n_rewards, m0, S0, H, om[i].data(), os[i].data(), orw[i].data(),
-                                  traj ? otr[i].data() : nullptr);
-            if (rc[i] != PILCO_OK) grp->fail_all();
-        });
-    for (auto& t : th) t.join();
-    for (int i = 0; i < n; ++i) ctxs[i]->group.reset();
-    for (int i = 0; i < n; ++i)
-        if (rc[i] != PILCO_OK) {
-            if (i != 0) c0->err = "rank " + std::to_string(i) + ": " + ctxs[i]->err;
-            return rc[i];
-        }
+    if (int r = run_group(ctxs, n, "rollout_group", [&](int i) {
+            return pilco_rollout(ctxs[i], policy, rewards, n_rewards, m0, S0, H, om[i].data(), os[i].data(), orw[i].data(), traj ? otr[i].data() : nullptr);
+        }))
+        return r;
     int mm = 0;
     for (int i = 1; i < n; ++i)
         if (memcmp(om[i].data(), om[0].data(), sizeof(double) * E) || memcmp(os[i].data(), os[0].data(), sizeof(double) * E * E) ||
@@ -346,36 +356,17 @@ int pilco_rollout_group(pilco_ctx** ctxs, int n, const pilco_policy* policy, con
     return PILCO_OK;
 }
 
-// Value and gradient of one sharded rollout over n contexts of THIS process (see pilco_rollout_group): every context runs
-// pilco_rollout_grad on a host thread; the per-step exchange of the forward chain and the one all-gather of the per-pair
-// Jacobian records are done by copies between host barriers.  Outputs of every rank: reward [n], dW [n][U*E], db [n][U].
+// Value and gradient of one sharded rollout over n contexts of THIS process: every context runs pilco_rollout_grad; the
+// per-step exchange of the forward chain and the one all-gather of the Jacobian records are done by copies between host
+// barriers.  Outputs of every rank: reward [n], dW [n][U*E], db [n][U].
 int pilco_rollout_grad_group(pilco_ctx** ctxs, int n, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
                              const double* m0, const double* S0, int H, double* reward, double* dW, double* db) {
     if (!ctxs || n <= 0 || !ctxs[0]) return PILCO_E_SHAPE;
-    pilco_ctx* c0 = ctxs[0];
-    if (!policy || !reward || !dW || !db) return fail(c0, PILCO_E_SHAPE, "rollout_grad_group: null pointer");
-    for (int i = 0; i < n; ++i)
-        if (!ctxs[i] || ctxs[i]->nranks != n || ctxs[i]->rank != i || ctxs[i]->comm)
-            return fail(c0, PILCO_E_STATE, "rollout_grad_group: context i must be shard_set(i, n) and have no communicator");
+    if (!policy || !reward || !dW || !db) return fail(ctxs[0], PILCO_E_SHAPE, "rollout_grad_group: null pointer");
     const int E = policy->state_dim, U = policy->control_dim;
-    auto grp = std::make_shared<PeerGroup>();
-    grp->ctxs.assign(ctxs, ctxs + n);
-    for (int i = 0; i < n; ++i) ctxs[i]->group = grp;
-    std::vector<int> rc(n, PILCO_OK);
-    std::vector<std::thread> th;
-    for (int i = 0; i < n; ++i)
-        th.emplace_back([&, i] {
-            rc[i] = pilco_rollout_grad(ctxs[i], policy, rewards, n_rewards, m0, S0, H, reward + i, dW + (size_t)i * U * E, db + (size_t)i * U);
-            if (rc[i] != PILCO_OK) grp->fail_all();
-        });
-    for (auto& t : th) t.join();
-    for (int i = 0; i < n; ++i) ctxs[i]->group.reset();
-    for (int i = 0; i < n; ++i)
-        if (rc[i] != PILCO_OK) {
-            if (i != 0) c0->err = "rank " + std::to_string(i) + ": " + ctxs[i]->err;
-            return rc[i];
-        }
-    return PILCO_OK;
+    return run_group(ctxs, n, "rollout_grad_group", [&](int i) {
+        return pilco_rollout_grad(ctxs[i], policy, rewards, n_rewards, m0, S0, H, reward + i, dW + (size_t)i * U * E, db + (size_t)i * U);
+    });
 }
 
 // ... and for an RbfController (pilco_rollout_grad_rbf on every context; the policy GP is not sharded: every rank evaluates
@@ -384,31 +375,12 @@ int pilco_rollout_grad_rbf_group(pilco_ctx** ctxs, int n, const pilco_policy* po
                                  const double* m0, const double* S0, int H, const double* Xp, const double* Yp, const double* lsp,
                                  const double* noisep, int bf, double* reward, double* dX, double* dY, double* dls) {
     if (!ctxs || n <= 0 || !ctxs[0]) return PILCO_E_SHAPE;
-    pilco_ctx* c0 = ctxs[0];
-    if (!policy || !reward || !dX || !dY || !dls) return fail(c0, PILCO_E_SHAPE, "rollout_grad_rbf_group: null pointer");
-    for (int i = 0; i < n; ++i)
-        if (!ctxs[i] || ctxs[i]->nranks != n || ctxs[i]->rank != i || ctxs[i]->comm)
-            return fail(c0, PILCO_E_STATE, "rollout_grad_rbf_group: context i must be shard_set(i, n) and have no communicator");
+    if (!policy || !reward || !dX || !dY || !dls) return fail(ctxs[0], PILCO_E_SHAPE, "rollout_grad_rbf_group: null pointer");
     const int E = policy->state_dim, U = policy->control_dim;
-    auto grp = std::make_shared<PeerGroup>();
-    grp->ctxs.assign(ctxs, ctxs + n);
-    for (int i = 0; i < n; ++i) ctxs[i]->group = grp;
-    std::vector<int> rc(n, PILCO_OK);
-    std::vector<std::thread> th;
-    for (int i = 0; i < n; ++i)
-        th.emplace_back([&, i] {
-            rc[i] = pilco_rollout_grad_rbf(ctxs[i], policy, rewards, n_rewards, m0, S0, H, Xp, Yp, lsp, noisep, bf, reward + i,
-                                           dX + (size_t)i * bf * E, dY + (size_t)i * bf * U, dls + (size_t)i * U * E);
-            if (rc[i] != PILCO_OK) grp->fail_all();
-        });
-    for (auto& t : th) t.join();
-    for (int i = 0; i < n; ++i) ctxs[i]->group.reset();
-    for (int i = 0; i < n; ++i)
-        if (rc[i] != PILCO_OK) {
-            if (i != 0) c0->err = "rank " + std::to_string(i) + ": " + ctxs[i]->err;
-            return rc[i];
-        }
-    return PILCO_OK;
+    return run_group(ctxs, n, "rollout_grad_rbf_group", [&](int i) {
+        return pilco_rollout_grad_rbf(ctxs[i], policy, rewards, n_rewards, m0, S0, H, Xp, Yp, lsp, noisep, bf, reward + i, dX + (size_t)i * bf * E,
+                                      dY + (size_t)i * bf * U, dls + (size_t)i * U * E);
+    });
 }
 
 // ------------------------------------------------------------------ peer exchange (include/pilco_hip.h)
