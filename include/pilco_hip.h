@@ -166,6 +166,33 @@ int pilco_propagate(pilco_ctx* ctx, const pilco_policy* policy, const double* m_
  * with PILCO_E_SHAPE before any launch. */
 int pilco_policy_action(pilco_ctx* ctx, const pilco_policy* policy, const double* m, const double* s, double* M, double* S, double* V);
 int pilco_reward_eval(pilco_ctx* ctx, const pilco_reward_term* rewards, int n_rewards, int state_dim, const double* m, const double* s, double* muR, double* sR);
+/* Particle rollout through the learned dynamics (extension): P sampled trajectories of H steps, all on
+ * the device, to hold against the Gaussians pilco_rollout propagates.  One step of particle p, D = E + U:
+ *   u = the policy's deterministic action at x = controller.compute_action(x, 0)[0] (pilco/models/pilco.py:115):
+ *       LINEAR  max_action * sin(x W^T + b);   RBF  max_action * exp(-0.5e-6) * sin(sum_i beta_ui k_u(x, c_i)), the policy GP
+ *       of PILCO_SLOT_POLICY (exp(-0.5e-6): the reference's S - diag(variance - 1e-6) at s = 0, controllers.py:117);
+ *       NONE  no control, D = E;  squash = 0: the argument of the sine itself
+ *   (mu_e, v_e) = the posterior of output e at [x, u] -- what pilco_gp_predict_points returns (exact GP or FITC on the
+ *       slot's shared Z); at s = 0 the moment matching of mgpr.py:91-149 gives exactly this Gaussian
+ *   x'_e = x_e + mu_e + sqrt(max(v_e [+ likelihood variance_e], 0)) * eps[t][p][e]     (the GP predicts differences,
+ *       pilco.py:138-153)
+ * x0 (P,E) initial particles.  eps (H,P,E) standard-normal draws, or NULL: generated on the device from seed (Philox4x32-10
+ * and Box-Muller, csrc/philox_normal.h: a draw depends on (seed, t, p, e) only).  observation_noise 0: latent variance
+ * (what moment matching propagates); 1: + likelihood variance.
+ * mean (H+1,E), cov (H+1,E,E): empirical moments of the particles after every step, row 0 = x0; the covariance divides by
+ * P (P = 1 gives zeros).  reward_steps (H, may be NULL): mean over the particles of the reward terms at zero covariance --
+ * exponential exp(-0.5 (x-t) W (x-t)^T), linear W.x, combined by coef -- of the PRE-step states 0..H-1 (the convention of
+ * pilco_rollout).  particles (H+1,P,E) and eps_out (H,P,E), the draws actually used: may be NULL.
+ * A particle's trajectory depends on its own x0 row and its own draws only: the same bits alone or in any batch.  The sums
+ * behind mean, cov and reward_steps run in a fixed order (no floating-point atomics): particles in index order inside blocks
+ * of 128, the blocks in index order; the same particles give the same bits.  All H steps are enqueued in one pass -- one upload,
+ * one download, one synchronisation; the particles are chunked like pilco_gp_predict_points: bounded memory for any P.
+ * Needs the dynamics slot's own factorisation (factorises if it is not current).  PILCO_E_STATE on a sharded or multi-rank
+ * context, after pilco_gp_set_factors, or for an RBF policy whose slot is not factorised; PILCO_E_SHAPE for P <= 0, H < 0, a
+ * null x0 / mean / cov or a policy whose dimensions do not match the slot. */
+int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                            const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
+                            double* mean, double* cov, double* reward_steps, double* particles, double* eps_out);
 
 /* ------------------------------------------------------------------ reverse mode
  * The reference differentiates training_loss with TensorFlow's autodiff (pilco/models/pilco.py:85-90);

@@ -102,6 +102,9 @@ int pilco_debug_last_route(const pilco_ctx* ctx, int* out, int n);
  * the one-launch small step with / without a reward workgroup */
 #define PILCO_GEOMETRY_WORDS 14
 int pilco_debug_geometry(pilco_ctx* ctx, int* out, int n);
+/* Test aid: the deterministic actions pilco_rollout_particles acts with -- its action kernel alone (k_particle_head,
+ * csrc/particles.hip) at P states x (P, E): u (P, U).  Policy checks and PILCO_E_* codes as pilco_rollout_particles. */
+int pilco_debug_particle_actions(pilco_ctx* ctx, const pilco_policy* policy, const double* x, int P, double* u);
 /* per-workgroup (start, end) stamps of the last prep launch, n values (developer aid) */
 int pilco_debug_blocks(pilco_ctx* ctx, unsigned long long* out, int n);
 /* developer aid: raw copy of a work buffer (0 row operands At, 1 column operands Wt | vcol, 2 reverse-pass row moments, 3 column sums, 4 beta) */

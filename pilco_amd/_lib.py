@@ -78,6 +78,8 @@ SIGNATURES = {
     "pilco_gp_predict_points": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "pilco_rollout": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                 _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                          _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "pilco_gp_predict_vjp": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout_tape": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                      _dp, _dp, _dp, _dp, _dp]),
@@ -110,6 +112,7 @@ SIGNATURES = {
     "pilco_debug_blocks": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.c_int]),
     "pilco_debug_last_route": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "pilco_debug_geometry": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
+    "pilco_debug_particle_actions": (C.c_int, [_vp, C.POINTER(PolicyStruct), _dp, C.c_int, _dp]),
     "pilco_debug_buffer": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_long]),
     "pilco_debug_sk_boundary": (C.c_int, [C.c_int] * 8),
     "pilco_debug_sk_pair_waves": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
@@ -404,6 +407,40 @@ class Context:
         if want_traj:
             return mH, SH, rew, traj
         return mH, SH, rew
+
+    def rollout_particles(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_particles=False):
+        """P sampled trajectories of H steps through the learned dynamics, on the device (pilco_rollout_particles):
+        x0 (P, E) initial particles; eps (H, P, E) standard-normal draws, or None: generated on the device from ``seed``.
+        Returns mean (H+1, E), cov (H+1, E, E), reward_steps (H,), particles (H+1, P, E) or None, the draws used (H, P, E)."""
+        E = policy["state_dim"]
+        p, k1 = self._policy(policy)
+        r, k2 = self._rewards(rewards, E)
+        x0 = _f64(x0)
+        if x0.ndim != 2 or x0.shape[1] != E:
+            raise ValueError(f"initial particles must be (P, {E})")
+        P, H = x0.shape[0], int(H)
+        if eps is not None:
+            eps = _f64(eps)
+            if eps.shape != (H, P, E):
+                raise ValueError(f"draws must be ({H}, {P}, {E})")
+        mean = np.empty((H + 1, E))
+        cov = np.empty((H + 1, E, E))
+        rew = np.empty((max(H, 0),))
+        parts = np.empty((H + 1, P, E)) if want_particles else None
+        used = np.empty((H, P, E))
+        self._chk(self.lib.pilco_rollout_particles(self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps),
+                                                   C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), 1 if observation_noise else 0,
+                                                   _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used)))
+        return mean, cov, rew, parts, used
+
+    def particle_actions(self, policy, x):
+        """Test aid: the actions (P, U) the particle rollout acts with at the states x (P, E) (pilco_debug_particle_actions)."""
+        E, U = policy["state_dim"], policy["control_dim"]
+        p, k1 = self._policy(policy)
+        x = _f64(x).reshape(-1, E)
+        u = np.empty((x.shape[0], U))
+        self._chk(self.lib.pilco_debug_particle_actions(self.h, C.byref(p), _ptr(x), x.shape[0], _ptr(u)))
+        return u
 
     def rollout_batch(self, policies, rewards, m0, S0, H):
         """B independent rollouts of the same model in flight together (pilco_rollout_batch): policies: list of B policy

@@ -1,0 +1,394 @@
+// Particle rollouts through the learned dynamics: pilco_rollout_particles.  DESIGN.md section 13, docs/particles.md.
+// P sampled trajectories of H steps, device resident, to hold against the Gaussians the moment matching propagates.
+// One step, per chunk of particles (the chunks of pilco_gp_predict_points: at most PP_KS_BUDGET doubles of cross-covariance):
+//   k_particle_head   the action u = policy(x) of every particle and the transposed, padded block [x, u] launch_gram reads
+//   predict_points_device (predict.hip)   the posterior (mu_e, v_e) of every output at [x, u]: two launches
+//   k_particle_tail   the draw (given, or Philox4x32-10 + Box-Muller: philox_normal.h), x'_e = x_e + mu_e + sqrt(max(v_e, 0)) eps,
+//                     and the reward of the pre-step state
+// and then, over ALL particles of the step at once (so nothing of it depends on the chunking):
+//   k_particle_partials / k_particle_finish   mean, covariance and mean reward
+// Every kernel up to the tail works on a particle with that particle's own row and draws only: a trajectory has the same bits
+// alone or in any batch (k_predict_points gives every test point a fixed order of its own).
+//
+// ORDER OF THE SUMS behind mean, cov and reward_steps (no floating-point atomics anywhere): the particles are cut into blocks
+// of PT_BLOCK = 128 consecutive indices; inside a block one thread per quantity adds the particles in index order; the
+// blocks' partial sums are added in block order.  The moments are taken about c = the step's particle 0 (shifted data: no
+// cancellation against |x|^2): S1_a = sum (x_a - c_a), S2_ab = sum (x_a - c_a)(x_b - c_b);
+//   mean_a = c_a + S1_a / P,   cov_ab = S2_ab / P - (S1_a / P)(S1_b / P),   reward = (sum r_p) / P.
+// The same particles in the same order give the same bits, whatever P is chunked into; P = 1 gives a zero covariance exactly.
+#include "philox_normal.h"
+#include "predict.h"
+
+namespace pilco {
+
+constexpr int PT_BLOCK = 128;
+
+struct ParticleHeadArgs {
+    const double* x;   // [P][E] the step's states
+    double* Xt;        // [D][ldt] the chunk's test points [x, u], transposed; zero past ntc
+    int p0, ntc, ldt, E, U, kind, squash;
+    const double *W, *b, *maxact;             // LinearController [U][E], [U]; scale of the squash [U]
+    const double *pc, *pls, *pvar, *pbeta;    // RbfController (policy slot): centres [E][pnpad], lengthscales [U][E], variances [U], beta [U][pnpad]
+    int pn, pnpad;
+};
+
+__global__ __launch_bounds__(256) void k_particle_head(ParticleHeadArgs a) {
+    const int E = a.E, U = a.U, ldt = a.ldt;
+    __shared__ double il_s[MAX_D * MAX_D / 4];   // RbfController: 1 / lengthscale [U][E]  (U + E <= MAX_D)
+    if (a.kind == PILCO_POLICY_RBF)
+        for (int q = threadIdx.x; q < U * E; q += 256) il_s[q] = 1.0 / a.pls[q];
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ldt) return;
+    if (i >= a.ntc) {
+        for (int d = 0; d < E + U; ++d) a.Xt[(long)d * ldt + i] = 0.0;
+        return;
+    }
+    const double* xr = a.x + (long)(a.p0 + i) * E;
+    for (int e = 0; e < E; ++e) a.Xt[(long)e * ldt + i] = xr[e];
+    for (int k = 0; k < U; ++k) {
+        double s = 0.0, scale = a.maxact[k];
+        if (a.kind == PILCO_POLICY_LINEAR) {
+            for (int e = 0; e < E; ++e) s = fma(xr[e], a.W[k * E + e], s);
+            s += a.b[k];
+        } else {
+            const double vk = a.pvar[k];
+            for (int c = 0; c < a.pn; ++c) {
+                double r2 = 0.0;
+                for (int e = 0; e < E; ++e) {
+                    const double d = (xr[e] - a.pc[(long)e * a.pnpad + c]) * il_s[k * E + e];
+                    r2 = fma(d, d, r2);
+                }
+                s = fma(a.pbeta[(long)k * a.pnpad + c], vk * exp(-0.5 * r2), s);
+            }
+            scale *= exp(-0.5e-6);   // squash_sin of a variance of 1e-6: S - diag(variance - 1e-6) at s = 0
+        }
+        a.Xt[(long)(E + k) * ldt + i] = a.squash ? scale * sin(s) : s;
+    }
+}
+
+struct ParticleReward {
+    int kind;
+    double coef;
+    const double *W, *t;   // exponential: [E][E], [E]; linear: [E]
+};
+
+struct ParticleTailArgs {
+    const double* x;        // [P][E] the step's states
+    double* xn;             // [P][E] the next states
+    const double *mu, *var; // [E][ldt] posterior of the chunk
+    const double* noise;    // [E] likelihood variances (observation_noise), or nullptr
+    const double* eps_in;   // [P][E] the step's draws, or nullptr: generated here
+    double* eps_out;        // [P][E] the draws used, or nullptr
+    double* rew;            // [P] reward of the pre-step state
+    unsigned long long seed;
+    int t, p0, ntc, ldt, E, n_rewards;
+    ParticleReward rw[MAX_REWARD_TERMS];
+};
+
+__device__ __forceinline__ double particle_reward(const ParticleTailArgs& a, const double* xr) {
+    const int E = a.E;
+    double total = 0.0;
+    for (int k = 0; k < a.n_rewards; ++k) {
+        const ParticleReward& r = a.rw[k];
+        double v = 0.0;
+        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
+            double q = 0.0;
+            for (int i = 0; i < E; ++i) {
+                double row = 0.0;
+                for (int j = 0; j < E; ++j) row = fma(r.W[i * E + j], xr[j] - r.t[j], row);
+                q = fma(xr[i] - r.t[i], row, q);
+            }
+            v = exp(-0.5 * q);
+        } else {
+            for (int i = 0; i < E; ++i) v = fma(r.W[i], xr[i], v);
+        }
+        total = fma(r.coef, v, total);
+    }
+    return total;
+}
+
+__global__ __launch_bounds__(256) void k_particle_tail(ParticleTailArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.ntc) return;
+    const int E = a.E, ldt = a.ldt;
+    const long p = a.p0 + i;
+    const double* xr = a.x + p * E;
+    double* xn = a.xn + p * E;
+    for (int j = 0; 2 * j < E; ++j) {
+        double z[2];
+        if (a.eps_in) {
+            z[0] = a.eps_in[p * E + 2 * j];
+            z[1] = (2 * j + 1 < E) ? a.eps_in[p * E + 2 * j + 1] : 0.0;
+        } else {
+            philox_normal_pair(a.seed, (uint32_t)a.t, (uint32_t)p, (uint32_t)j, &z[0], &z[1]);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int e = 2 * j + h;
+            if (e >= E) break;
+            double v = a.var[(long)e * ldt + i];
+            if (a.noise) v += a.noise[e];
+            const double sd = sqrt(fmax(v, 0.0));
+            xn[e] = (xr[e] + a.mu[(long)e * ldt + i]) + sd * z[h];
+            if (a.eps_out) a.eps_out[p * E + e] = z[h];
+        }
+    }
+    a.rew[p] = particle_reward(a, xr);
+}
+
+struct ParticleStatArgs {
+    const double* x;     // [P][E]
+    const double* rew;   // [P], or nullptr (the last states: no reward)
+    double* part;        // [nblk][Q] partial sums, Q = E + E*E + 1
+    double* out;         // [Q] mean | cov | mean reward
+    int P, E, nblk;
+};
+
+// block b: particles PT_BLOCK b .. ; thread q adds quantity q over them in index order
+__global__ __launch_bounds__(PT_BLOCK) void k_particle_partials(ParticleStatArgs a) {
+    const int E = a.E, Q = E + E * E + 1, ldx = E + 2;
+    __shared__ double xs[PT_BLOCK * (MAX_D + 2)];   // [particle][x - c | reward]
+    const int i = threadIdx.x;
+    const long p = (long)blockIdx.x * PT_BLOCK + i;
+    for (int e = 0; e < E; ++e) xs[i * ldx + e] = (p < a.P) ? a.x[p * E + e] - a.x[e] : 0.0;
+    xs[i * ldx + E] = (p < a.P && a.rew) ? a.rew[p] : 0.0;
+    __syncthreads();
+    for (int q = threadIdx.x; q < Q; q += PT_BLOCK) {
+        double s = 0.0;
+        if (q < E || q == Q - 1) {
+            const int col = q < E ? q : E;
+            for (int k = 0; k < PT_BLOCK; ++k) s += xs[k * ldx + col];
+        } else {
+            const int ab = q - E, ca = ab / E, cb = ab - ca * E;
+            for (int k = 0; k < PT_BLOCK; ++k) s = fma(xs[k * ldx + ca], xs[k * ldx + cb], s);
+        }
+        a.part[(long)blockIdx.x * Q + q] = s;
+    }
+}
+
+// thread q: the blocks' partial sums of quantity q in block order, then the moment it stands for
+__global__ __launch_bounds__(PT_BLOCK) void k_particle_finish(ParticleStatArgs a) {
+    const int E = a.E, Q = E + E * E + 1;
+    const int q = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (q >= Q) return;
+    auto total = [&](int col) {
+        double s = 0.0;
+        for (int b = 0; b < a.nblk; ++b) s += a.part[(long)b * Q + col];
+        return s;
+    };
+    const double n = (double)a.P;
+    if (q < E) {
+        a.out[q] = a.x[q] + total(q) / n;
+    } else if (q == Q - 1) {
+        a.out[q] = total(q) / n;
+    } else {
+        const int ab = q - E, ca = ab / E, cb = ab - ca * E;
+        const double ma = total(ca) / n, mb = total(cb) / n;
+        a.out[q] = total(q) / n - ma * mb;
+    }
+}
+
+}  // namespace pilco
+
+using namespace pilco;
+
+namespace {
+struct StreamDrain {   // the staging vectors of the call are locals: nothing of the stream may outlive them
+    hipStream_t st;
+    ~StreamDrain() { (void)hipStreamSynchronize(st); }
+};
+}  // namespace
+
+// the policy against the dynamics slot (and, RbfController, the policy slot)
+static int check_policy(pilco_ctx* ctx, const pilco_policy* policy) {
+    const Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    if (!policy) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: null policy");
+    const int E = s.E, D = s.D, U = D - E;
+    if (policy->state_dim != E || policy->control_dim != U || U < 0 || D > MAX_D)
+        return fail(ctx, PILCO_E_SHAPE, "rollout_particles: policy dims do not match the model (state_dim must be E, control_dim D-E)");
+    if (policy->kind < 0 || policy->kind > 2) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: unknown policy kind");
+    if (policy->kind == PILCO_POLICY_NONE && U != 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: policy NONE needs D == E");
+    if (policy->kind != PILCO_POLICY_NONE && U == 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: a policy needs control_dim > 0");
+    if (policy->kind == PILCO_POLICY_LINEAR && (!policy->W || !policy->b))
+        return fail(ctx, PILCO_E_SHAPE, "rollout_particles: linear policy needs W and b");
+    if (policy->kind == PILCO_POLICY_RBF) {
+        const Slot& ps = ctx->slot[PILCO_SLOT_POLICY];
+        if (!ps.factor_valid || ps.M > 0) return fail(ctx, PILCO_E_STATE, "rollout_particles: RBF policy slot has no current (exact) factorisation");
+        if (ps.D != E || ps.E != U) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: RBF policy GP must map state_dim -> control_dim");
+    }
+    return PILCO_OK;
+}
+
+// the policy's parameters into the staging vector hp (W[U*E] b[U] maxact[U]) and the action kernel's arguments; dev: where hp goes
+static void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double>& hp, size_t& off, const double* dev,
+                         ParticleHeadArgs& ha) {
+    const Slot &s = ctx->slot[PILCO_SLOT_DYNAMICS], &ps = ctx->slot[PILCO_SLOT_POLICY];
+    const int E = s.E, U = s.D - s.E;
+    ha.E = E; ha.U = U; ha.kind = policy->kind; ha.squash = policy->squash;
+    if (policy->kind == PILCO_POLICY_LINEAR) {
+        memcpy(&hp[off], policy->W, sizeof(double) * U * E);
+        ha.W = dev + off; off += (size_t)U * E;
+        memcpy(&hp[off], policy->b, sizeof(double) * U);
+        ha.b = dev + off; off += U;
+    }
+    for (int u = 0; u < U; ++u) hp[off + u] = policy->max_action ? policy->max_action[u] : 1.0;
+    ha.maxact = dev + off; off += U;
+    if (policy->kind == PILCO_POLICY_RBF) {
+        ha.pc = ps.Xt.p; ha.pls = ps.ls.p; ha.pvar = ps.var.p; ha.pbeta = ps.beta.p;
+        ha.pn = ps.N; ha.pnpad = ps.Npad;
+    }
+}
+
+extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                       const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                       int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
+                                       double* eps_out) {
+    if (int r = check_slot(ctx, PILCO_SLOT_DYNAMICS)) return r;
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    if (ctx->nranks != 1 || ctx->comm || s.shW > 1) return fail(ctx, PILCO_E_STATE, "rollout_particles: single rank only");
+    if (!s.has_data || !s.has_hyp) return fail(ctx, PILCO_E_STATE, "rollout_particles needs set_data and set_hyp first");
+    if (s.user_factors)
+        return fail(ctx, PILCO_E_STATE, "rollout_particles: the slot holds factors set by pilco_gp_set_factors, not its own factorisation");
+    if (P <= 0 || H < 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: P must be positive and H non-negative");
+    if (!x0 || !mean || !cov) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: null x0, mean or cov");
+    if (int r = check_policy(ctx, policy)) return r;
+    const int E = s.E, D = s.D, U = D - E;
+    if (n_rewards < 0 || n_rewards > MAX_REWARD_TERMS || (n_rewards > 0 && !rewards))
+        return fail(ctx, PILCO_E_SHAPE, "rollout_particles: 0..4 reward terms supported");
+    for (int i = 0; i < n_rewards; ++i) {
+        if (rewards[i].kind != PILCO_REWARD_EXPONENTIAL && rewards[i].kind != PILCO_REWARD_LINEAR)
+            return fail(ctx, PILCO_E_SHAPE, "reward: unknown kind");
+        if (!rewards[i].W) return fail(ctx, PILCO_E_SHAPE, "reward: W is required");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!s.factor_valid)
+        if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
+    if (!s.pred) s.pred = new PredictWork();
+    PredictWork& pw = *s.pred;
+    hipStream_t st = ctx->st;
+    const PredictModel md = predict_model_of(s, 0, E);
+    const int npad = md.npad;
+    const int ntc_max = std::min(round_up(P, 64), predict_chunk_cap(E, npad));
+    const size_t PE = (size_t)P * E;
+    const int Q = E + E * E + 1, nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
+    const int nslab = particles ? H + 1 : 2;
+    const bool keep_eps = H > 0 && (eps || eps_out);
+    // parameters: W[U*E] b[U] maxact[U], then per reward W[E*E] t[E] (exponential) or W[E] (linear)
+    std::vector<double> hp((size_t)U * E + 2 * U + (size_t)MAX_REWARD_TERMS * (E * E + E) + 8, 0.0);
+    std::vector<double> hstats((size_t)(H + 1) * Q);
+    ENSURE(pw.Xt, (size_t)D * ntc_max);
+    ENSURE(pw.Ks, (size_t)E * ntc_max * npad);
+    ENSURE(pw.out, (size_t)2 * E * ntc_max);
+    ENSURE(pw.pt_x, (size_t)nslab * PE);
+    if (keep_eps) ENSURE(pw.pt_eps, (size_t)H * PE);
+    ENSURE(pw.pt_rew, (size_t)P);
+    ENSURE(pw.pt_part, (size_t)nblk * Q);
+    ENSURE(pw.pt_stats, hstats.size());
+    ENSURE(pw.pt_par, hp.size());
+
+    ParticleHeadArgs ha{};
+    ParticleTailArgs ta{};
+    size_t off = 0;
+    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ha);
+    ta.n_rewards = n_rewards;
+    for (int i = 0; i < n_rewards; ++i) {
+        ParticleReward& r = ta.rw[i];
+        r.kind = rewards[i].kind;
+        r.coef = rewards[i].coef;
+        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
+            memcpy(&hp[off], rewards[i].W, sizeof(double) * E * E);
+            r.W = pw.pt_par.p + off; off += (size_t)E * E;
+            if (rewards[i].t) memcpy(&hp[off], rewards[i].t, sizeof(double) * E);   // (NULL: the zeros hp holds)
+            r.t = pw.pt_par.p + off; off += E;
+        } else {
+            memcpy(&hp[off], rewards[i].W, sizeof(double) * E);
+            r.W = pw.pt_par.p + off; off += E;
+            r.t = r.W;
+        }
+    }
+    StreamDrain drain{st};
+    // one upload: parameters, initial particles, the caller's draws
+    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
+    if (eps && H > 0) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
+
+    ta.E = E; ta.seed = seed;
+    ta.noise = observation_noise ? s.noise.p : nullptr;
+    ta.rew = pw.pt_rew.p;
+    ParticleStatArgs sa{};
+    sa.P = P; sa.E = E; sa.nblk = nblk; sa.part = pw.pt_part.p;
+    auto slab = [&](int t) { return pw.pt_x.p + (size_t)(particles ? t : (t & 1)) * PE; };
+    auto stats = [&](int t, bool with_reward) {   // moments of the states after t steps (and the mean reward of step t - 1)
+        sa.x = slab(t);
+        sa.rew = with_reward ? pw.pt_rew.p : nullptr;
+        sa.out = pw.pt_stats.p + (size_t)t * Q;
+        hipLaunchKernelGGL(k_particle_partials, dim3(nblk), dim3(PT_BLOCK), 0, st, sa);
+        hipLaunchKernelGGL(k_particle_finish, dim3((Q + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sa);
+    };
+    stats(0, false);
+    for (int t = 0; t < H; ++t) {
+        ha.x = ta.x = slab(t);
+        ta.xn = slab(t + 1);
+        ta.t = t;
+        ta.eps_in = eps ? pw.pt_eps.p + (size_t)t * PE : nullptr;
+        ta.eps_out = (!eps && eps_out) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
+        for (int p0 = 0; p0 < P; p0 += ntc_max) {
+            const int ntc = std::min(ntc_max, P - p0), ldt = round_up(ntc, 64);
+            double *out_mean = pw.out.p, *out_var = pw.out.p + (size_t)E * ldt;
+            ha.Xt = pw.Xt.p; ha.p0 = p0; ha.ntc = ntc; ha.ldt = ldt;
+            hipLaunchKernelGGL(k_particle_head, dim3((ldt + 255) / 256), dim3(256), 0, st, ha);
+            if (int r = predict_points_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, out_mean, out_var)) return r;
+            ta.mu = out_mean; ta.var = out_var; ta.p0 = p0; ta.ntc = ntc; ta.ldt = ldt;
+            hipLaunchKernelGGL(k_particle_tail, dim3((ntc + 255) / 256), dim3(256), 0, st, ta);
+        }
+        stats(t + 1, true);   // (its reward word: the mean reward of the pre-step states of step t)
+    }
+    HIPCHK(hipGetLastError());
+    // one download, one synchronisation
+    HIPCHK(hipMemcpyAsync(hstats.data(), pw.pt_stats.p, sizeof(double) * hstats.size(), hipMemcpyDeviceToHost, st));
+    if (particles) HIPCHK(hipMemcpyAsync(particles, pw.pt_x.p, sizeof(double) * (H + 1) * PE, hipMemcpyDeviceToHost, st));
+    if (eps_out && !eps && H > 0) HIPCHK(hipMemcpyAsync(eps_out, pw.pt_eps.p, sizeof(double) * H * PE, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (eps_out && eps && H > 0) memcpy(eps_out, eps, sizeof(double) * H * PE);
+    for (int t = 0; t <= H; ++t) {
+        const double* row = &hstats[(size_t)t * Q];
+        memcpy(mean + (size_t)t * E, row, sizeof(double) * E);
+        memcpy(cov + (size_t)t * E * E, row + E, sizeof(double) * E * E);
+        if (t > 0 && reward_steps) reward_steps[t - 1] = row[Q - 1];
+    }
+    return PILCO_OK;
+}
+
+extern "C" int pilco_debug_particle_actions(pilco_ctx* ctx, const pilco_policy* policy, const double* x, int P, double* u) {
+    if (int r = check_slot(ctx, PILCO_SLOT_DYNAMICS)) return r;
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    if (!s.has_data) return fail(ctx, PILCO_E_STATE, "particle_actions needs set_data first");
+    if (int r = check_policy(ctx, policy)) return r;
+    const int E = s.E, D = s.D, U = D - E;
+    if (P <= 0 || !x || (U > 0 && !u)) return fail(ctx, PILCO_E_SHAPE, "particle_actions: null pointer or P <= 0");
+    if (U == 0) return PILCO_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!s.pred) s.pred = new PredictWork();
+    PredictWork& pw = *s.pred;
+    const int ldt = round_up(P, 64);
+    std::vector<double> hp((size_t)U * E + 2 * U + 8, 0.0);
+    ENSURE(pw.pt_x, (size_t)P * E);
+    ENSURE(pw.Xt, (size_t)D * ldt);
+    ENSURE(pw.pt_par, hp.size());
+    ParticleHeadArgs ha{};
+    size_t off = 0;
+    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ha);
+    ha.x = pw.pt_x.p; ha.Xt = pw.Xt.p; ha.p0 = 0; ha.ntc = P; ha.ldt = ldt;
+    StreamDrain drain{ctx->st};
+    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x, sizeof(double) * P * E, hipMemcpyHostToDevice, ctx->st));
+    hipLaunchKernelGGL(k_particle_head, dim3((ldt + 255) / 256), dim3(256), 0, ctx->st, ha);
+    HIPCHK(hipGetLastError());
+    std::vector<double> ut((size_t)U * ldt);
+    HIPCHK(hipMemcpyAsync(ut.data(), pw.Xt.p + (size_t)E * ldt, sizeof(double) * ut.size(), hipMemcpyDeviceToHost, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < U; ++k) u[(size_t)p * U + k] = ut[(size_t)k * ldt + p];
+    return PILCO_OK;
+}

@@ -1,0 +1,31 @@
+// GP posterior at deterministic inputs, shared by predict.hip (pilco_gp_predict_points) and particles.hip
+// (pilco_rollout_particles): the per-slot work buffers, the operands of one model and the device-to-device routine.
+#pragma once
+#include "ctx.h"
+
+constexpr size_t PP_KS_BUDGET = size_t(1) << 24;   // doubles of cross-covariance per chunk (128 MB)
+
+// the per-call buffers of the predictions, and the FITC operands of per-output inducing inputs (a slot of its own whose
+// data, targets and hyper-parameters are views of the parent slot's); pt_*: the particle rollout's buffers (particles.hip)
+struct PredictWork {
+    DevBuf raw, Xt, Ks, out;
+    Slot fitc;
+    DevBuf pt_x, pt_eps, pt_rew, pt_part, pt_stats, pt_par;
+};
+
+// The operator blocks and the points of the cross-covariance of Eu outputs of one model (device pointers).
+struct PredictModel {
+    const double* Pt;      // [D][npad] training / inducing points, transposed
+    long sP;               // doubles between the outputs' point sets (0: one set shared by every output)
+    const double *ls, *sf2, *sn2;   // [Eu][D], [Eu], [Eu]
+    const double *L, *iAt, *beta;   // [Eu][npad][npad] L^{-1}, FITC: Am^{-1} Luu^{-1} (nullptr: exact GP), [Eu][npad]
+    int n, npad, D, Eu;
+};
+PredictModel predict_model_of(const Slot& s, int e0, int Eu);   // the slot's own factorisation, outputs e0 .. e0 + Eu - 1
+// test points per chunk: the cross-covariance of a chunk is at most PP_KS_BUDGET doubles (a multiple of 64)
+inline int predict_chunk_cap(int Eu, int npad) { return std::max(64, (int)(PP_KS_BUDGET / ((size_t)Eu * npad)) / 64 * 64); }
+// One chunk, device to device: Xt [D][ldt] holds ntc test points (transposed, ldt a multiple of 64); Ks is scratch of
+// Eu * ldt * npad doubles; out_mean, out_var [Eu][ldt].  Two launches (the cross-covariances, the walk over the operator)
+// on ctx->st; does not wait for the stream.
+int predict_points_device(pilco_ctx* ctx, const PredictModel& m, const double* Xt, int ntc, int ldt, double* Ks, double* out_mean,
+                          double* out_var);

@@ -5,7 +5,9 @@
 // The cross-covariances of a chunk of test points are built by launch_gram; one kernel then walks the row blocks of the stacked
 // operator [L^{-1}; (iAt;) beta^T] on v_mfma_f64_16x16x4_f64 and squares and sums every product tile in registers: the product
 // W = L^{-1} K* never leaves the chip.
-#include "ctx.h"
+// predict_points_device is that pair of launches, device to device and without a wait (predict.h): pilco_gp_predict_points
+// wraps it in upload, download and synchronisation; the particle rollout (particles.hip) calls it per chunk of particles.
+#include "predict.h"
 #include "mm_device.h"
 
 namespace pilco {
@@ -13,7 +15,6 @@ namespace pilco {
 constexpr int PP_CT = 2;                    // 16-point column tiles per workgroup: 32 test points
 constexpr int PP_RB = 4;                    // 16-row blocks per work unit: 64 operator rows
 constexpr int PP_PTS = 16 * PP_CT;
-constexpr size_t PP_KS_BUDGET = size_t(1) << 24;   // doubles of cross-covariance per chunk (128 MB)
 
 struct PredictArgs {
     const double* Ks;     // [Eu][ldt][npad]: k(test point t, training / inducing point k); zero past n and past the chunk
@@ -146,17 +147,10 @@ __global__ __launch_bounds__(256) void k_predict_points(PredictArgs a) {
 
 using namespace pilco;
 
-// the per-call buffers of the predictions, and the FITC operands of per-output inducing inputs (a slot of its own whose
-// data, targets and hyper-parameters are views of the parent slot's)
-struct PredictWork {
-    DevBuf raw, Xt, Ks, out;
-    Slot fitc;
-};
-
 void predict_release(Slot& s) {
     if (!s.pred) return;
     PredictWork& p = *s.pred;
-    for (DevBuf* b : {&p.raw, &p.Xt, &p.Ks, &p.out}) b->release();
+    for (DevBuf* b : {&p.raw, &p.Xt, &p.Ks, &p.out, &p.pt_x, &p.pt_eps, &p.pt_rew, &p.pt_part, &p.pt_stats, &p.pt_par}) b->release();
     Slot& f = p.fitc;
     for (ChainGraph* cg : {&f.g_fact, &f.g_fitc, &f.g_fitc_nlml}) chain_graph_release(*cg);
     for (DevBuf* b : {&f.Xt, &f.Yt, &f.Zt, &f.ls, &f.var, &f.noise, &f.K, &f.Linv, &f.iK, &f.beta, &f.Tscr, &f.ksplit_ws, &f.vec,
@@ -198,6 +192,40 @@ static int factorize_own_z(pilco_ctx* ctx, Slot& s, PredictWork& pw, const doubl
     return PILCO_OK;
 }
 
+PredictModel predict_model_of(const Slot& s, int e0, int Eu) {
+    const bool sparse = s.M > 0;
+    PredictModel m{};
+    m.n = sparse ? s.M : s.N;
+    m.npad = sparse ? s.npad : s.Npad;
+    m.D = s.D;
+    m.Eu = Eu;
+    const long mat = (long)m.npad * m.npad;
+    m.Pt = sparse ? s.Zt.p : s.Xt.p;
+    m.sP = 0;
+    m.ls = s.ls.p + (size_t)e0 * s.D;
+    m.sf2 = s.var.p + e0;
+    m.sn2 = s.noise.p + e0;
+    m.L = s.Linv.p + e0 * mat;
+    m.iAt = sparse ? s.iAt.p + e0 * mat : nullptr;
+    m.beta = s.beta.p + (size_t)e0 * m.npad;
+    return m;
+}
+
+int predict_points_device(pilco_ctx* ctx, const PredictModel& m, const double* Xt, int ntc, int ldt, double* Ks, double* out_mean,
+                          double* out_var) {
+    hipStream_t st = ctx->st;
+    launch_gram(st, Xt, ldt, ntc, m.Pt, m.npad, m.n, m.D, m.ls, m.sf2, m.Eu, Ks, ldt, m.npad, 0, nullptr, 0.0, 0, m.sP);
+    PredictArgs a{};
+    a.Ks = Ks; a.sKs = (long)ldt * m.npad;
+    a.L = m.L; a.iAt = m.iAt; a.sL = (long)m.npad * m.npad;
+    a.beta = m.beta; a.var = m.sf2; a.noise = m.sn2;
+    a.out_mean = out_mean; a.out_var = out_var;
+    a.n = m.n; a.npad = m.npad; a.G = (m.n + 63) / 64; a.ntc = ntc; a.ldt = ldt;
+    hipLaunchKernelGGL(k_predict_points, dim3(ldt / PP_PTS, m.Eu), dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return PILCO_OK;
+}
+
 extern "C" int pilco_gp_predict_points(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int output, const double* Z_all,
                                        double* mean, double* var) {
     if (int r = check_slot(ctx, slot)) return r;
@@ -216,42 +244,30 @@ extern "C" int pilco_gp_predict_points(pilco_ctx* ctx, int slot, const double* X
     PredictWork& pw = *s.pred;
     hipStream_t st = ctx->st;
     const int D = s.D, Eu = output < 0 ? s.E : 1, e0 = output < 0 ? 0 : output;
-    const bool sparse = s.M > 0;
-    const int n = sparse ? s.M : s.N, npad = sparse ? s.npad : s.Npad;
-    const long mat = (long)npad * npad;
     // the operator blocks and the points of the cross-covariance, for outputs e0 ..
-    const double *Pt = sparse ? s.Zt.p : s.Xt.p, *ls = s.ls.p + (size_t)e0 * D, *sf2 = s.var.p + e0, *sn2 = s.noise.p + e0;
-    const double *L = s.Linv.p + e0 * mat, *iAt = sparse ? s.iAt.p + e0 * mat : nullptr, *beta = s.beta.p + (size_t)e0 * npad;
-    long sP = 0;
+    PredictModel md = predict_model_of(s, e0, Eu);
     if (Z_all) {
         if (int r = factorize_own_z(ctx, s, pw, Z_all, e0, Eu)) return r;
         const Slot& f = pw.fitc;
-        Pt = f.Zt.p; sP = f.Zstride;
-        L = f.Linv.p; iAt = f.iAt.p; beta = f.beta.p;
+        md.Pt = f.Zt.p; md.sP = f.Zstride;
+        md.L = f.Linv.p; md.iAt = f.iAt.p; md.beta = f.beta.p;
     }
+    const int npad = md.npad;
     // chunks of test points: the cross-covariance of a chunk is at most PP_KS_BUDGET doubles
-    const int ntc_cap = std::max(64, (int)(PP_KS_BUDGET / ((size_t)Eu * npad)) / 64 * 64);
-    const int ntc_max = std::min(round_up(Nt, 64), ntc_cap);
+    const int ntc_max = std::min(round_up(Nt, 64), predict_chunk_cap(Eu, npad));
     ENSURE(pw.raw, (size_t)ntc_max * D);
     ENSURE(pw.Xt, (size_t)D * ntc_max);
     ENSURE(pw.Ks, (size_t)Eu * ntc_max * npad);
     ENSURE(pw.out, (size_t)2 * Eu * ntc_max);
     for (int t0 = 0; t0 < Nt; t0 += ntc_max) {
         const int ntc = std::min(ntc_max, Nt - t0), ldt = round_up(ntc, 64);
+        double *out_mean = pw.out.p, *out_var = pw.out.p + (size_t)Eu * ldt;
         HIPCHK(hipMemcpyAsync(pw.raw.p, Xs + (size_t)t0 * D, sizeof(double) * ntc * D, hipMemcpyHostToDevice, st));
         launch_transpose_points(st, pw.raw.p, ntc, D, pw.Xt.p, ldt);
-        launch_gram(st, pw.Xt.p, ldt, ntc, Pt, npad, n, D, ls, sf2, Eu, pw.Ks.p, ldt, npad, 0, nullptr, 0.0, 0, sP);
-        PredictArgs a{};
-        a.Ks = pw.Ks.p; a.sKs = (long)ldt * npad;
-        a.L = L; a.iAt = iAt; a.sL = mat;
-        a.beta = beta; a.var = sf2; a.noise = sn2;
-        a.out_mean = pw.out.p; a.out_var = pw.out.p + (size_t)Eu * ldt;
-        a.n = n; a.npad = npad; a.G = (n + 63) / 64; a.ntc = ntc; a.ldt = ldt;
-        hipLaunchKernelGGL(k_predict_points, dim3(ldt / PP_PTS, Eu), dim3(256), 0, st, a);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpy2DAsync(mean + t0, sizeof(double) * Nt, a.out_mean, sizeof(double) * ldt, sizeof(double) * ntc, Eu,
+        if (int r = predict_points_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, out_mean, out_var)) return r;
+        HIPCHK(hipMemcpy2DAsync(mean + t0, sizeof(double) * Nt, out_mean, sizeof(double) * ldt, sizeof(double) * ntc, Eu,
                                 hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpy2DAsync(var + t0, sizeof(double) * Nt, a.out_var, sizeof(double) * ldt, sizeof(double) * ntc, Eu,
+        HIPCHK(hipMemcpy2DAsync(var + t0, sizeof(double) * Nt, out_var, sizeof(double) * ldt, sizeof(double) * ntc, Eu,
                                 hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));   // (the chunk's buffers are reused by the next)
     }

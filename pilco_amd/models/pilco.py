@@ -13,6 +13,19 @@ from .mgpr import MGPR
 from .smgpr import SMGPR
 
 
+class ParticleTrajectories:
+    """What PILCO.sample_trajectories returns: mean (n+1, E) and cov (n+1, E, E) of the particles after every step (row 0:
+    the initial particles), reward (1, 1) = reward_steps.sum() -- comparable with predict(...)[2] --, reward_steps (n,),
+    particles (n+1, P, E) or None, eps (n, P, E): the standard-normal draws used."""
+
+    def __init__(self, mean, cov, reward_steps, particles, eps):
+        self.mean, self.cov, self.reward_steps, self.particles, self.eps = mean, cov, reward_steps, particles, eps
+        self.reward = np.asarray(reward_steps, np.float64).sum().reshape(1, 1)
+
+    def __repr__(self):
+        return "ParticleTrajectories(steps=%d, state_dim=%d, reward=%.6g)" % (self.mean.shape[0] - 1, self.mean.shape[1], self.reward[0, 0])
+
+
 class PILCO:
     def __init__(self, data, num_induced_points=None, horizon=30, controller=None,
                  reward=None, m_init=None, S_init=None, name=None, ctx=None):
@@ -178,6 +191,32 @@ class PILCO:
         if self._host_reward_terms():
             R = R + self._host_reward_value(traj, n)
         return M, S, R, traj
+
+    def sample_trajectories(self, m_x, s_x, n, num_particles=1000, seed=0, eps=None, x0=None, observation_noise=False,
+                            return_particles=False):
+        """Extension: num_particles trajectories of n steps sampled through the learned dynamics on the device
+        (pilco_rollout_particles), to hold against the Gaussians predict() propagates.  Every particle acts with
+        compute_action(x) and moves by a draw from the GP posterior at [x, u] (latent variance; observation_noise adds the
+        likelihood variance).  x0 (P, E): the initial particles; otherwise x0 = m_x + z sqrt(s_x) with z from
+        np.random.default_rng(seed) and the symmetric square root of s_x (eigenvalues clipped at zero: s_x = 0 works).
+        eps (n, P, E): the standard-normal draws of the steps; otherwise generated on the device from ``seed``.  An SMGPR
+        runs on the shared inducing inputs of the rollout.  Returns a ParticleTrajectories."""
+        if self._host_reward_terms():
+            raise NotImplementedError("sample_trajectories: reward terms evaluated on the host are not supported on particles; "
+                                      "ask for return_particles=True and evaluate them on the returned particles")
+        E = self.state_dim
+        if x0 is None:
+            m = np.asarray(m_x, np.float64).reshape(1, E)
+            w, V = np.linalg.eigh(0.5 * (np.asarray(s_x, np.float64).reshape(E, E) + np.asarray(s_x, np.float64).reshape(E, E).T))
+            root = (V * np.sqrt(np.clip(w, 0.0, None))) @ V.T
+            x0 = m + np.random.default_rng(seed).standard_normal((int(num_particles), E)) @ root
+        x0 = np.asarray(x0, np.float64).reshape(-1, E)
+        self.mgpr._user_factors = None
+        self.mgpr._ensure_factorized()
+        mean, cov, rew, parts, used = self.ctx.rollout_particles(self._policy_spec(), self._reward_terms(), x0, int(n), eps=eps,
+                                                                 seed=seed, observation_noise=observation_noise,
+                                                                 want_particles=return_particles)
+        return ParticleTrajectories(mean, cov, rew, parts, used)
 
     # pilco.py:138-153
     def propagate(self, m_x, s_x):
