@@ -85,7 +85,7 @@ int pilco_get_pair_timing(pilco_ctx* ctx, float* ms_pair, int* n_pair_launches);
  * prep / glue kernels (100 MHz wall clock); later calls copy the 32 slots of the last launch. */
 int pilco_debug_timestamps(pilco_ctx* ctx, unsigned long long* out32);
 /* Test aid: what the host planner chose for the last pilco_rollout / pilco_rollout_tape / pilco_rollout_grad* on this context
- * (a batch: its lane 0).  Host bookkeeping only.  Copies the first min(n, 12) words:
+ * (a batch: its lane 0).  Host bookkeeping only.  Copies the first min(n, 13) words:
  *   [0] entry: 1 rollout, 2 value-and-gradient rollout
  *   [1] step: 0 none, 1 fused head + pair launch, 2 one-launch small step, 3 three-kernel step,
  *       4 fused heads with the RbfController's own launches, 5 peer exchange
@@ -93,7 +93,8 @@ int pilco_debug_timestamps(pilco_ctx* ctx, unsigned long long* out32);
  *   [3] DT of the operand kernel   [4] KP of the pair kernel (KC = KP / 4)   [5] vsep
  *   [6] the step's O(N^2) work: 0/1/2 pair kernel variant, 3 inside the head, 4 reverse-sweep launch, 5 reverse sweep inside the head
  *   [7] tape: 0 none, 1 plain, 2 Jacobian   [8] H   [9] npad
- *   [10] reverse chain: 0 none, 1 device, 2 host   [11] LDS bytes of a k_rev_step workgroup (device chain) */
+ *   [10] reverse chain: 0 none, 1 device, 2 host   [11] LDS bytes of a k_rev_step workgroup (device chain)
+ *   [12] exchange of the ranks' Jacobian records: 0 none, 1 communicator (ncclAllGather), 2 contexts of one process */
 int pilco_debug_last_route(const pilco_ctx* ctx, int* out, int n);
 /* Test aid: the step geometry of the dynamics slot's current workspace (after a rollout; host bookkeeping only).  Copies the
  * first min(n, 14) words: [0] npad [1] local pairs PL [2] local outputs EL [3] operand row chunks NCH [4] mean row chunks NCHM

@@ -678,7 +678,7 @@ class Context:
         self._chk(self.lib.pilco_debug_timestamps(self.h, buf if read else None))
         return list(buf)
 
-    ROUTE_FIELDS = ("entry", "step", "policy", "DT", "KP", "vsep", "pair", "tape", "H", "npad", "chain", "rev_lds")
+    ROUTE_FIELDS = ("entry", "step", "policy", "DT", "KP", "vsep", "pair", "tape", "H", "npad", "chain", "rev_lds", "exchange")
 
     def last_route(self):
         """What the host planner chose for the last rollout / gradient rollout (include/pilco_hip_dev.h: pilco_debug_last_route),

@@ -44,7 +44,8 @@ enum RouteWord {
     ROUTE_NPAD = 9,      // padded point count of the dynamics model
     ROUTE_CHAIN = 10,    // reverse chain of a gradient rollout: 0 = none, 1 = device (rev.hip), 2 = host (grad.hip)
     ROUTE_REV_LDS = 11,  // device chain: LDS bytes of one k_rev_step workgroup (above 65536: the raised per-kernel limit)
-    PILCO_ROUTE_WORDS = 12,
+    ROUTE_EXCHANGE = 12, // records' exchange of a gradient rollout: 0 = none, 1 = communicator (ncclAllGather), 2 = group of one process
+    PILCO_ROUTE_WORDS = 13,
 };
 enum StepKind { STEP_NONE = 0, STEP_FUSED = 1, STEP_SMALL = 2, STEP_THREE = 3, STEP_FUSED_RBF = 4, STEP_PEER = 5 };   // ROUTE_STEP
 
@@ -90,6 +91,7 @@ struct PeerGroup {
     int waiting = 0;
     unsigned long generation = 0;
     bool failed = false;
+    int first_failed = -1;   // the rank whose own error failed the group (the others only report that somebody failed)
     bool arrive_and_wait() {   // false when the group has failed
         std::unique_lock<std::mutex> lk(mu);
         if (failed) return false;
@@ -103,8 +105,9 @@ struct PeerGroup {
         cv.wait(lk, [&] { return generation != gen || failed; });
         return !failed;
     }
-    void fail_all() {
+    void fail_all(int rank) {
         std::lock_guard<std::mutex> lk(mu);
+        if (!failed) first_failed = rank;
         failed = true;
         cv.notify_all();
     }

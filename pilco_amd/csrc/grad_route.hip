@@ -262,18 +262,23 @@ int plan_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_ter
     // PILCO_GRAD_MODE=0 / pilco_set_grad_mode(ctx, 0): plain tape, and the O(N^2) adjoint of every step on the device again --
     // the two agree to rounding
     gr.chain = GRAD_CHAIN_ADJOINT;
-    if (ctx->grad_mode == 0) return PILCO_OK;
     const bool sharded = ctx->nranks != 1 || ctx->comm;
+    // the plain tape's per-step adjoint (pilco_gp_predict_vjp) is single rank only: a sharded call that would take it is refused
+    // here, on every rank alike and before its collective forward tape is enqueued
+    auto adjoint = [&](const char* why) {
+        return sharded ? fail(ctx, PILCO_E_STATE, std::string("rollout_grad: ") + why + " takes the plain tape, which is single rank only") : PILCO_OK;
+    };
     if (sharded && !ctx->comm && !ctx->group)
         return fail(ctx, PILCO_E_STATE, "rollout_grad: a sharded context needs a communicator (pilco_comm_init) or pilco_rollout_grad_group");
+    if (ctx->grad_mode == 0) return adjoint("grad_mode 0");
     if (int r = setup_rollout(ctx, policy, rewards, n_rewards, H, true, gc.plan)) return r;
     const int E = gc.plan.E, U = gc.plan.U, D = gc.plan.D;
-    if (D > 14) return PILCO_OK;   // third-moment records and their LDS working set are sized for D <= 14
+    if (D > 14) return adjoint("an input width D > 14");   // third-moment records and their LDS working set are sized for D <= 14
     // a rollout whose per-step buffers would need more than PILCO_JAC_GB (default 32) takes the plain tape too
     const JacBufs jb = jac_bufs(ctx->slot[0]);
     double cap_gb = 32.0;
     if (const char* ev = getenv("PILCO_JAC_GB")) cap_gb = atof(ev);
-    if ((double)(jb.rowmom + jb.cpart + jb.head + jb.part) * 8.0 * (double)std::max(H, 1) > cap_gb * 1e9) return PILCO_OK;
+    if ((double)(jb.rowmom + jb.cpart + jb.head + jb.part) * 8.0 * (double)std::max(H, 1) > cap_gb * 1e9) return adjoint("a rollout over PILCO_JAC_GB");
     gr.chain = GRAD_CHAIN_RECORDS;
     if (sharded && H > 0) gr.exchange = ctx->comm ? GRAD_XCH_COMM : GRAD_XCH_GROUP;   // (no steps: no records to exchange)
     if (linear && ctx->dev_chain && rev_chain_supported(E, U, D)) {
@@ -365,4 +370,5 @@ void grad_route_record(pilco_ctx* ctx, const GradRoute& route) {
     ctx->route[ROUTE_ENTRY] = 2;
     ctx->route[ROUTE_CHAIN] = route.chain == GRAD_CHAIN_DEVICE ? 1 : 2;
     ctx->route[ROUTE_REV_LDS] = route.rev_lds;
+    ctx->route[ROUTE_EXCHANGE] = route.exchange == GRAD_XCH_COMM ? 1 : route.exchange == GRAD_XCH_GROUP ? 2 : 0;
 }

@@ -90,7 +90,8 @@ int peer_detach(pilco_ctx* ctx) {
 
 // Run one call on every context of a group of n contexts of THIS process (rank i = ctxs[i], any devices), each on a host
 // thread of its own, with the group's host barrier (PeerGroup) attached for the duration: call(i) is context i's call.  A
-// rank that fails releases the others; the first failing rank's error is the group's, labelled with its rank on ctxs[0].
+// rank that fails releases the others; the error of the rank that failed FIRST is the group's, labelled with its rank on
+// ctxs[0] (the released ranks fail too, with "another member failed": theirs would hide which member the caller has to mend).
 template <class Call>
 static int run_group(pilco_ctx** ctxs, int n, const char* who, Call&& call) {
     pilco_ctx* c0 = ctxs[0];
@@ -105,16 +106,14 @@ static int run_group(pilco_ctx** ctxs, int n, const char* who, Call&& call) {
     for (int i = 0; i < n; ++i)
         th.emplace_back([&, i] {
             rc[i] = call(i);
-            if (rc[i] != PILCO_OK) grp->fail_all();
+            if (rc[i] != PILCO_OK) grp->fail_all(i);
         });
     for (auto& t : th) t.join();
     for (int i = 0; i < n; ++i) ctxs[i]->group.reset();
-    for (int i = 0; i < n; ++i)
-        if (rc[i] != PILCO_OK) {
-            if (i != 0) c0->err = "rank " + std::to_string(i) + ": " + ctxs[i]->err;
-            return rc[i];
-        }
-    return PILCO_OK;
+    const int i = grp->first_failed;
+    if (i < 0) return PILCO_OK;
+    if (i != 0) c0->err = "rank " + std::to_string(i) + ": " + ctxs[i]->err;
+    return rc[i];
 }
 
 extern "C" {

@@ -65,10 +65,12 @@ def oracle_trajectory(c, d, zero_iK=False):
     return _trajectory(lambda m, s: tp.predict_given_factorizations_pairs(pts, d["ls"], d["var"], m, s, iK, beta), c, d)
 
 
-def pair_step(pts, ls, var, m, s, iK, beta, drop_point=False, drop_dim=False):
+def pair_step(pts, ls, var, m, s, iK, beta, drop_point=False, drop_dim=False, pair_hook=None):
     """mgpr.py:91-149 with the pair sums per output pair (b <= a).  drop_point: the last point is left out of the pair sums
     (beta_a' L beta_b and tr(iK_a L)) while iK and beta stay those of all points; drop_dim: the last input dimension is left
-    out of the pair exponent log(var_a) + log(var_b) + k_a + k_b + maha only."""
+    out of the pair exponent log(var_a) + log(var_b) + k_a + k_b + maha only.  pair_hook: called with the finished pair sums
+    {(a, b): value} (b <= a; what the ranks of a sharded step exchange, up to the mean product) and returns the ones the
+    covariance is assembled from."""
     m = m.reshape(1, -1)
     E, D = ls.shape
     zeta = pts - m
@@ -88,7 +90,7 @@ def pair_step(pts, ls, var, m, s, iK, beta, drop_point=False, drop_dim=False):
     for a in range(E):
         k.append(np.log(var[a]) - 0.5 * np.sum((zk / ls[a, :nd]) ** 2, 1))
     n = pts.shape[0] - (1 if drop_point else 0)
-    S = np.empty((E, E))
+    vals = {}
     for a in range(E):
         for b in range(a + 1):
             R = s @ np.diag(1.0 / ls[a] ** 2 + 1.0 / ls[b] ** 2) + eye
@@ -101,13 +103,20 @@ def pair_step(pts, ls, var, m, s, iK, beta, drop_point=False, drop_dim=False):
             val = beta[a, :n] @ L @ beta[b, :n]
             if a == b:
                 val -= np.sum(iK[a][:n, :n] * L)
-            S[a, b] = S[b, a] = val / np.sqrt(np.linalg.det(R))
+            vals[(a, b)] = val / np.sqrt(np.linalg.det(R))
+    if pair_hook:
+        vals = pair_hook(vals)
+    S = np.empty((E, E))
+    for (a, b), val in vals.items():
+        S[a, b] = S[b, a] = val
     S = S + np.diag(var) - np.outer(M, M)
     return M, S, V
 
 
-def perturbed_trajectory(c, d, **damage):
+def perturbed_trajectory(c, d, zero_iK=False, **damage):
     iK, beta = factors(c, d)
+    if zero_iK:
+        iK = np.zeros_like(iK)
     pts = points(c, d)
     return _trajectory(lambda m, s: pair_step(pts, d["ls"], d["var"], m, s, iK, beta, **damage), c, d)
 
