@@ -1,5 +1,5 @@
 // Reverse pass of one moment-matching step: k_mm_bwd_pair / _post / _fin.
-#include "grad_layout.h"
+#include "lds_layout.h"
 #include "mm_device.h"
 #include "rev_local.h"
 
@@ -37,9 +37,7 @@ namespace pilco {
 #ifndef BWD_FAIR
 #define BWD_FAIR 1   // the sweep's workgroups lower their issue priority as they advance through their column range (measured:
 #endif               // sweep 98.8 -> 96.9 us, three A/B repetitions in one call; rising priority: no gain; 0 = off)
-constexpr int BWD_CH = 64;   // columns staged per LDS chunk (one wave-wide row segment)
-constexpr int BWD_SCR_H = 40, BWD_SCR_R = 72, BWD_SCR_W = 4 * BWD_SCR_R;   // column-sum scratch of a wave (doubles): half / register strides, size
-__host__ __device__ constexpr int bwd_tp(int kp) { return kp <= 16 ? 17 : kp + 1; }   // pitch of the staged column-major tile (doubles): operand rows + 1 (odd: conflict-free)
+// (BWD_CH columns are staged per LDS chunk, at pitch bwd_tp; BWD_SCR_*: a wave's column-sum scratch -- lds_layout.h: SweepLds)
 // sum_{q < n} base[q * stride] with the loads of a batch of B issued together (a plain loop serialises one global
 // latency per term: these kernels are latency-bound); fixed summation order
 template <int B>
@@ -65,9 +63,10 @@ __device__ void bwd_head(const MMModel& md, const MMWork& wk, const double* __re
                          double* __restrict__ head, double* sm, const double* __restrict__ in_s = nullptr) {
     if (!in_s) in_s = wk.in_s;
     const int D = md.D, E = md.E, t = threadIdx.x, nc = 2 * D, nI = D * D;
-    double* G0 = sm;               // [D][2D]
-    double* G1 = G0 + D * nc;      // [D][2D]
-    double* lam = G1 + D * nc;     // [D]
+    const HeadLds L = head_lds(D);
+    double* G0 = sm + L.G0;        // [D][2D]
+    double* G1 = sm + L.G1;        // [D][2D]
+    double* lam = sm + L.lam;      // [D]
     const double* Mbar = bars;
     const double* Sbar = bars + E;
     const double* Vbar = bars + E + E * E;
@@ -137,7 +136,8 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
                                                     double* __restrict__ cpart, int njs, const double* __restrict__ bars,
                                                     double* __restrict__ head, double* __restrict__ npart) {
     __shared__ double tab[FEXP_TN];
-    extern __shared__ __attribute__((aligned(16))) double csl[];   // [4][jw]  (head workgroups: Gauss-Jordan scratch)
+    static_assert(sizeof(tab) == SWEEP_STATIC_BYTES, "mm_bwd_split counts the exp table beside the dynamic LDS");
+    extern __shared__ __attribute__((aligned(16))) double csl[];   // SweepLds  (head workgroups: HeadLds)
     kernarg_warm<(int)(sizeof(MMModel) + sizeof(MMWork)) + 56 + 64>();
     if ((int)blockIdx.y >= wk.PL) {   // spare workgroups: the step's D x D inverses, one per output / pair
         const int h = ((int)blockIdx.y - wk.PL) * (int)(gridDim.x * gridDim.z) + (int)(blockIdx.z * gridDim.x + blockIdx.x);
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
     const double* iKa = (diag && md.iK) ? md.iK + mm_ik_blk(md, a) * npad * npad : nullptr;
     // column range of this split: the npad / 16 column tiles dealt as evenly as they go (njs need not divide them)
     const int ct = npad / 16, jbeg = 16 * (int)((long)js * ct / njs), jend = 16 * (int)((long)(js + 1) * ct / njs);
-    const int jw = jend - jbeg, jws = 16 * ((ct + njs - 1) / njs);   // jws: LDS slice stride (the widest split)
+    const int jw = jend - jbeg, jws = sweep_jws(npad, njs);   // jws: LDS slice stride (the widest split)
     const int rbase = rb * 64 * BWD_RT, ibase = rbase + w * 16 * BWD_RT;
     // a diagonal pair starts at the staged chunk that holds the workgroup's first row (nothing left of it is swept)
     const int jstart = diag ? min(jend, jbeg + BWD_CH * (max(0, rbase - jbeg) / BWD_CH)) : jbeg;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
     // transpose a2 (K = column, N = operand row) -- without bank conflicts (pitch 17 doubles); the next chunk is in
     // flight in registers while the current one is evaluated.  Only the iK stream of a diagonal pair stays a per-wave
     // buffer load.
-    constexpr int KPc = 4 * KC, NR = KPc + (VSEP ? 2 : 1), NST = (NR + 3) / 4, BWD_TP = bwd_tp(KPc), SB = BWD_CH * BWD_TP + 2 * BWD_CH;
+    constexpr int KPc = 4 * KC, NR = KPc + (VSEP ? 2 : 1), NST = (NR + 3) / 4, BWD_TP = bwd_tp(KPc), SB = bwd_stage_doubles(KPc);
     const __amdgpu_buffer_rsrc_t rIK = buf_rsrc_uniform(iKa ? iKa + (long)jbeg * npad : po.Wt);
     const double* vsrc = (const double*)((const char*)po.Wt + po.v0);   // (staged only when VSEP: otherwise v_j is row D + 1 of the contraction)
     unsigned ik_voff[BWD_RT];   // (the 4 r part of the row index rides in the scalar offset: 2 registers instead of 8)
@@ -190,7 +190,8 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
     int dsel[NMT];                       // operand rows contracted by the second product: w_j (d < D), the ones (d = D);
 #pragma unroll                           // lanes past that repeat row D: their result columns (d > D) are never read
     for (int m = 0; m < NMT; ++m) dsel[m] = 16 * m + lc <= D ? 16 * m + lc : D;
-    double* stg = csl + 4 * jws;         // [2][SB]
+    const SweepLds L = sweep_lds(jws, KPc);
+    double* stg = csl + L.stg;           // [2][SB]
     auto stage_load = [&](int jc, double (&sg)[NST]) {
 #pragma unroll
         for (int k = 0; k < NST; ++k) {
@@ -220,7 +221,7 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
     // rows of one 16-lane read group on the four quarters of the bank row and the two 8-lane runs of a store group on
     // different halves of the 32 store banks: no conflicts either way (the plain [r][lr][lc] layout read back two-way: lanes
     // l and l + 8 of a group on the same banks -- SQ_LDS_BANK_CONFLICT was twice the useful LDS cycles, profiles/r04_grad_pmc_summary.json)
-    double* scr = csl + 4 * jws + 2 * SB + w * BWD_SCR_W;
+    double* scr = csl + L.scr + w * BWD_SCR_W;
     const int rd_jj = lane >> 2, rd_q = lane & 3;
     const double* rd_src = scr + (rd_jj >> 2) * BWD_SCR_R + (rd_jj & 3) * 8 + 2 * rd_q;
     double* wr_dst = scr + (lc >> 3) * BWD_SCR_H + lr * 8 + (lc & 7);
@@ -423,7 +424,8 @@ __global__ __launch_bounds__(256, (KC <= 4 && NMT == 1) ? 4 : BWD_LBW) void k_mm
     }
     // ---- epilogue 3: the four waves' G added in LDS (block by block: the staging area holds 4 x 256 doubles), one block
     // per workgroup to memory; N_ab's share for the serial link of a value-and-gradient rollout is entry (D, D)
-    double* red = stg;   // [4][256]  (2 SB + 4 * BWD_SCR_W >= 1024 doubles)
+    double* red = stg;   // [4][256]
+    static_assert(2 * SB + 4 * BWD_SCR_W >= 4 * 256, "the reduction buffer reuses the staging buffers and the scratch");
     double* gout = gpart + (((long)pl * njs + js) * gridDim.x + rb) * (NMT * NMT * 256);
     const int tN = ((D & 15) >> 2) * 64 + (D & 3) * 16 + (D & 15);   // entry of (d, e) = (D, D) inside its block
 #pragma unroll
@@ -460,11 +462,12 @@ __device__ void bwd_mean_partial(const MMModel& md, const double* __restrict__ i
                                  int nrc, double* __restrict__ mpart, double* sm) {
     const int D = md.D, npad = md.npad, t = threadIdx.x;
     const int nI = D * D, LD = D | 1;
-    double* T = sm;                 // [D][D]
-    double* zs = T + nI;            // [64][LD]
-    double* lv = zs + 64 * LD;      // [64]
-    double* lq = lv + 64;           // [64]
-    double* u = lq + 64;            // [D + 2]: u | mu | c_a
+    const MeanPartialLds L = mean_partial_lds(D);
+    double* T = sm + L.T;           // [D][D]
+    double* zs = sm + L.zs;         // [64][LD]
+    double* lv = sm + L.lv;         // [64]
+    double* lq = sm + L.lq;         // [64]
+    double* u = sm + L.u;           // [D + 2]: u | mu | c_a
     const double* hd = head + (long)a * (nI + D + 2);
     for (int e = t; e < nI + D + 2; e += 256) (e < nI ? T[e] : u[e - nI]) = hd[e];
     __syncthreads();
@@ -548,16 +551,16 @@ int mm_jac_ns(int D) { return (D + 1) * (D + 2) * (D + 3) / 6; }
 // columns f < 16, K = the points (4 per v_mfma_f64_16x16x4_f64): 4 LDS reads feed 1024 multiply-adds; entries f <= e are the
 // moments (the others are computed for nothing).  l_i itself: the quadratic form's rows dealt over the four waves (256
 // threads per 64-point block instead of 64).
-constexpr int JAC_MT = 8;   // row tiles: D1 (D1 + 1) / 2 <= 128 pairs (D <= 14)
 __device__ void bwd_mean_moments_mfma(const MMModel& md, const double* __restrict__ in_m, const double* __restrict__ head, int a, int rc,
                                       int nrc, double* __restrict__ mpart, double* sm) {
     const int D = md.D, D1 = D + 1, npad = md.npad, t = threadIdx.x, lane = t & 63, w = t >> 6, lr = lane >> 4, lc = lane & 15;
     const int nI = D * D, LD = 17, NS = D1 * (D1 + 1) * (D1 + 2) / 6, NPAIR = D1 * (D1 + 1) / 2, ntile = (NPAIR + 15) / 16;
-    double* T = sm;                 // [D][16]    rows zero-padded: the quadratic form runs over 16 columns without a condition
-    double* zs = T + 16 * 16;       // [64][17]   zeta (zeros past D) | 1 at column D   (odd row length: conflict-free column reads)
-    double* lv = zs + 64 * LD;      // [64]
-    double* qp = lv + 64;           // [4][64]  partial quadratic forms; later [4][256] for the waves' tiles
-    int* ptab = (int*)(qp + 4 * 256);   // [16 JAC_MT] pair row -> d | e << 8, or -1
+    constexpr MeanMomentsLds L = mean_moments_lds();
+    double* T = sm + L.T;           // [D][16]    rows zero-padded: the quadratic form runs over 16 columns without a condition
+    double* zs = sm + L.zs;         // [64][17]   zeta (zeros past D) | 1 at column D   (odd row length: conflict-free column reads)
+    double* lv = sm + L.lv;         // [64]
+    double* qp = sm + L.qp;         // [4][64]  partial quadratic forms; later [4][256] for the waves' tiles
+    int* ptab = (int*)(sm + L.ptab);    // [16 JAC_MT] pair row -> d | e << 8, or -1
     const double* hd = head + (long)a * (nI + D + 2);
     {
         const int r = t >> 4, c = t & 15;   // 256 threads: one entry of the padded [16][16] each
@@ -656,12 +659,13 @@ __device__ void bwd_mean_final(const MMModel& md, const double* __restrict__ bar
                                int nrc, const double* __restrict__ mpart, double* __restrict__ out, double* sm) {
     const int D = md.D, E = md.E, t = threadIdx.x;
     const int nI = D * D;
-    double* T = sm;                 // [D][D]
-    double* u = T + nI;             // [D + 2]: u | mu | c_a
-    double* sc = u + D + 2;         // [2]  phi
-    double* Th = sc + 2;            // [D]
-    double* red = Th + D;           // [nI + 2 D + 1]   H2q | wq | h | g
-    double* TH = red + nI + 2 * D + 1;  // [D][D]
+    const MeanFinalLds L = mean_final_lds(D);
+    double* T = sm + L.T;           // [D][D]
+    double* u = sm + L.u;           // [D + 2]: u | mu | c_a
+    double* sc = sm + L.sc;         // [2]  phi
+    double* Th = sm + L.Th;         // [D]
+    double* red = sm + L.red;       // [nI + 2 D + 1]   H2q | wq | h | g
+    double* TH = sm + L.TH;         // [D][D]
     const double* Vbar = bars + E + E * E;
     const double* hd = head + (long)a * (nI + D + 2);
     for (int e = t; e < nI + D + 2; e += 256) (e < nI ? T[e] : u[e - nI]) = hd[e];
@@ -731,7 +735,7 @@ struct BwdBatch {
 // time: ~8 us per workgroup where the block-by-block form needs ~50 (2 us of memory latency per 64-column block).
 template <int NMT>
 __device__ void bwd_pair_post(const MMModel& md, const MMWork& wk, const double* __restrict__ in_m, const double* __restrict__ gpart,
-                              const double* __restrict__ cpart, int njs, int nrb, double* o /* [1 + D + D*D]: global, or LDS behind sm's 6 * 256 (NMT = 1) */,
+                              const double* __restrict__ cpart, int njs, int nrb, double* o /* [1 + D + D*D]: global, or JacRecLds::Iv (NMT = 1) */,
                               int nrc, int pl, int rc, double* sm, double* cjl = nullptr) {
     const int npad = md.npad, D = md.D, E = md.E, t = threadIdx.x;
     const int lane = t & 63, w = t >> 6, lr = lane >> 4, lc = lane & 15;
@@ -739,9 +743,10 @@ __device__ void bwd_pair_post(const MMModel& md, const MMWork& wk, const double*
     int a, b;
     local_pair_ab(wk, E, pl, a, b);
     const bool diag = (a == b);
-    double* Gs = sm;                 // [GW][GW]  this chunk's share of G
-    double* Gc = Gs + GW * GW;       // [GW][GW]  ... and of the column side
-    double* red = Gc + GW * GW;      // [4][256]
+    constexpr PairPostLds L = pair_post_lds(NMT);
+    double* Gs = sm + L.Gs;          // [GW][GW]  this chunk's share of G
+    double* Gc = sm + L.Gc;          // [GW][GW]  ... and of the column side
+    double* red = sm + L.red;        // [4][256]
     if (njs == 0) {
         // one-launch small step (prep_device.h: small_sweep): every chunk-workgroup of the pair left TWO blocks, G and Gc (the
         // column side is already contracted); nrb = chunks per pair.  Chunk rc of nrc adds its share, as below.
@@ -1014,10 +1019,11 @@ __device__ void bwd_fin_pairs(const MMModel& md, const MMWork& wk, const double*
                               const double* __restrict__ head, double* __restrict__ out, double* sm) {
     const int D = md.D, E = md.E, t = threadIdx.x, pl = blockIdx.x;
     const int nI = D * D, rec = 1 + D + nI;
-    double* Pm = sm;               // [D][D]
-    double* lam = Pm + nI;         // [D + 2]: lambda | kappa
-    double* Iv = lam + D + 2;      // [rec]  summed partials (N | A | I)
-    double* PI = Iv + rec;         // [D][D]
+    const FinPairsLds L = fin_pairs_lds(D);
+    double* Pm = sm + L.Pm;        // [D][D]
+    double* lam = sm + L.lam;      // [D + 2]: lambda | kappa
+    double* Iv = sm + L.Iv;        // [rec]  summed partials (N | A | I)
+    double* PI = sm + L.PI;        // [D][D]
     const double* hd = head + (long)(E + pl) * (nI + D + 2);
     for (int e = t; e < nI + D + 2; e += 256) (e < nI ? Pm[e] : lam[e - nI]) = hd[e];
     for (int e = t; e < rec; e += 256) {
@@ -1064,13 +1070,14 @@ __device__ void jac_fin_output(const MMModel& md, const double* __restrict__ hea
                                const double* __restrict__ mpart, double* __restrict__ rec, double* sm) {
     const int D = md.D, D1 = D + 1, t = threadIdx.x;
     const int nI = D * D, n3 = nI * D, NS = D1 * (D1 + 1) * (D1 + 2) / 6;
-    double* T = sm;            // [D][D]
-    double* Hs = T + nI;       // [NS]
-    double* Th = Hs + NS;      // [D]
-    double* TH = Th + D;       // [D][D]   T H2
-    double* THT = TH + nI;     // [D][D]   T H2 T
-    double* W3 = THT + nI;     // [D][D][D]  W3[k][d][e] = sum_f H3(d,e,f) T[f][k]
-    double* Z3 = W3 + n3;      // [D][D][D]  Z3[k][r][e] = sum_d T[r][d] W3[k][d][e]
+    const JacFinOutputLds L = jac_fin_output_lds(D);
+    double* T = sm + L.T;      // [D][D]
+    double* Hs = sm + L.Hs;    // [NS]
+    double* Th = sm + L.Th;    // [D]
+    double* TH = sm + L.TH;    // [D][D]   T H2
+    double* THT = sm + L.THT;  // [D][D]   T H2 T
+    double* W3 = sm + L.W3;    // [D][D][D]  W3[k][d][e] = sum_f H3(d,e,f) T[f][k]
+    double* Z3 = sm + L.Z3;    // [D][D][D]  Z3[k][r][e] = sum_d T[r][d] W3[k][d][e]
     const double* hd = head + (long)a * (nI + D + 2);
     for (int e = t; e < nI; e += 256) T[e] = hd[e];
     const double c = hd[nI + D + 1];
@@ -1208,7 +1215,7 @@ __global__ __launch_bounds__(256, JAC_REC_LB) void k_mm_jac_rec(MMModel md, MMWo
                                                        double* __restrict__ jrec, long jstride, BwdBatch bb) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int D = md.D, E = md.E, t = threadIdx.x, z = blockIdx.y;
-    const int nI = D * D, rec = 1 + D + nI, NT2 = D * (D + 1) / 2, recp = 1 + D + NT2;
+    const int nI = D * D, NT2 = D * (D + 1) / 2, recp = 1 + D + NT2;
     gpart += (long)z * bb.gpart;
     cpart += (long)z * bb.cpart;
     mpart += (long)z * bb.part;
@@ -1222,13 +1229,14 @@ __global__ __launch_bounds__(256, JAC_REC_LB) void k_mm_jac_rec(MMModel md, MMWo
     }
     const int pl = blockIdx.x;
     JAC_STAMP(wk, 48, pl == 0 && z == 0 && t == 0);
-    double* Iv = sm + 6 * 256;     // [rec]  behind bwd_pair_post's Gs | Gc | red
-    double* Pm = Iv + rec;         // [D][D]
-    double* lam = Pm + nI;         // [D + 2]
-    double* PI = lam + D + 2;      // [2][D][D]
+    const JacRecLds L = jac_rec_lds(D, md.npad);
+    double* Iv = sm + L.Iv;        // [rec]  behind bwd_pair_post's Gs | Gc | red
+    double* Pm = sm + L.Pm;        // [D][D]
+    double* lam = sm + L.lam;      // [D + 2]
+    double* PI = sm + L.PI;        // [2][D][D]
     const double* hd = head + (long)(E + pl) * (nI + D + 2);
     for (int e = t; e < nI + D + 2; e += 256) (e < nI ? Pm[e] : lam[e - nI]) = hd[e];
-    bwd_pair_post<1>(md, wk, in_m, gpart, cpart, njs, nrb, Iv, 1, pl, 0, sm, sm + ((6 * 256 + rec + 3 * nI + D + 2 + 1) & ~1));   // cjl [npad] behind PI, 16-byte aligned
+    bwd_pair_post<1>(md, wk, in_m, gpart, cpart, njs, nrb, Iv, 1, pl, 0, sm, sm + L.cjl);   // cjl [npad] behind PI, 16-byte aligned
     __syncthreads();
     JAC_STAMP(wk, 52, pl == 0 && z == 0 && t == 0);
     jac_pair_record(D, Pm, lam, Iv, PI, jrec + (long)pl * recp);
@@ -1240,22 +1248,26 @@ size_t mm_jac_part_size(int D, int E, int P, int npad) {
     return (size_t)P * mm_bwd_rc(npad) * (1 + D + D * D) + (size_t)E * mm_bwd_rc(npad) * mm_jac_ns(D);
 }
 
-// the sweep kernel for this contraction width (KC = KP / 4 MFMA k-steps) and number of moment tiles
-static void launch_bwd_pair(hipStream_t st, dim3 grid, size_t lds, const MMModel& md, const MMWork& wk, double* rowmom, double* cpart,
-                            int njs, const double* bars, double* head, double* npart) {
+// The reverse sweep of a step (launch_mm_bwd, and launch_mm_sweep for the Jacobian tape): its grid -- the rows past P hold the
+// head workgroups -- and the kernel for this contraction width (KC = KP / 4 MFMA k-steps) and number of moment tiles.  Returns
+// the split it used (column splits, row blocks).
+struct SweepSplit {
+    int njs, nrb;
+};
+static SweepSplit launch_bwd_pair(hipStream_t st, const MMModel& md, const MMWork& wk, double* rowmom, double* cpart, const double* bars,
+                                  double* head, double* npart) {
+    const int P = wk.PL;
+    int njs, nrb;
+    mm_bwd_split(md.npad, md.E * (md.E + 1) / 2, wk.KP, &njs, &nrb);   // (the model's pairs, not this rank's: the split of a pair's sums is the same on every rank count)
+    const int nhead = md.E + P, per_row = nrb * njs;
+    const dim3 grid(nrb, P + (nhead + per_row - 1) / per_row, njs);
+    const size_t lds = sizeof(double) * lds_launch_sweep(md.npad, njs, wk.KP, md.D);
     const int kc = wk.KP / 4, nmt = (md.D + 16) / 16;
-    static bool lds_set = false;   // (the attribute is per function; set for every instantiation that may need > 64 KB)
-#define PBL(K_, M_)                                                                                                                  \
-    do {                                                                                                                             \
-        if (wk.vsep) {                                                                                                               \
-            if (lds > 65536) (void)hipFuncSetAttribute((const void*)k_mm_bwd_pair<K_, true, M_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_mm_bwd_pair<K_, true, M_>), grid, dim3(256), lds, st, md, wk, rowmom, cpart, njs, bars, head, npart); \
-        } else {                                                                                                                     \
-            if (lds > 65536) (void)hipFuncSetAttribute((const void*)k_mm_bwd_pair<K_, false, M_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_mm_bwd_pair<K_, false, M_>), grid, dim3(256), lds, st, md, wk, rowmom, cpart, njs, bars, head, npart); \
-        }                                                                                                                            \
+#define PBL(K_, M_)                                                                                                               \
+    do {                                                                                                                          \
+        if (wk.vsep) launch_lds<k_mm_bwd_pair<K_, true, M_>>(grid, dim3(256), lds, st, md, wk, rowmom, cpart, njs, bars, head, npart);  \
+        else launch_lds<k_mm_bwd_pair<K_, false, M_>>(grid, dim3(256), lds, st, md, wk, rowmom, cpart, njs, bars, head, npart);   \
     } while (0)
-    (void)lds_set;
     if (nmt == 1) {
         switch (kc) {
             case 1: PBL(1, 1); break;
@@ -1274,9 +1286,9 @@ static void launch_bwd_pair(hipStream_t st, dim3 grid, size_t lds, const MMModel
         PBL(9, 3);
     }
 #undef PBL
+    return {njs, nrb};
 }
 
-void mm_bwd_geometry(int npad, int Pg, int* njs, int* nrb);
 size_t mm_bwd_gpart_size(int npad, int P, int D) {   // one (16 NMT)^2 block per sweep workgroup (sized for the most column splits: 4)
     int njs, nrb;
     mm_bwd_geometry(npad, 1, &njs, &nrb);
@@ -1292,9 +1304,9 @@ size_t mm_bwd_cpart_size(int npad, int P) {
 size_t mm_jac_rowmom_size(int npad, int P) { return mm_bwd_gpart_size(npad, P, 1); }   // (the Jacobian tape serves D <= 14: one block)
 size_t mm_jac_cpart_size(int npad, int P, int) { return mm_bwd_cpart_size(npad, P); }
 size_t mm_jac_head_size(int D, int E, int P) { return (size_t)(E + P) * (D * D + D + 2); }
-int mm_jac_nt(int npad, int Pg) {   // Pg: pairs of the WHOLE model
+int mm_jac_nt(int npad, int Pg, int kp) {   // Pg: pairs of the WHOLE model
     int njs, nrb;
-    mm_bwd_geometry(npad, Pg, &njs, &nrb);
+    mm_bwd_split(npad, Pg, kp, &njs, &nrb);
     return njs * nrb;
 }
 
@@ -1303,15 +1315,7 @@ int mm_jac_nt(int npad, int Pg) {   // Pg: pairs of the WHOLE model
 // partials for the serial link.
 void launch_mm_sweep(hipStream_t st, const MMModel& md, const MMWork& wk, double* rowmom, double* cpart, double* head,
                      double* npart) {
-    const int P = wk.PL, E = md.E, D = md.D;
-    int njs, nrb;
-    mm_bwd_geometry(md.npad, md.E * (md.E + 1) / 2, &njs, &nrb);   // (the model's pairs, not this rank's: the split of a pair's sums is the same on every rank count)
-    const int nhead = E + P, per_row = nrb * njs;
-    dim3 grid(nrb, P + (nhead + per_row - 1) / per_row, njs);
-    const int nI = D * D;
-    const size_t lds_pair = sizeof(double) * std::max((size_t)4 * 16 * ((md.npad / 16 + njs - 1) / njs) + 2 * (BWD_CH * bwd_tp(wk.KP) + 2 * BWD_CH) + 4 * BWD_SCR_W, (size_t)4 * nI + D);
-    const double* bars = nullptr;
-    launch_bwd_pair(st, grid, lds_pair, md, wk, rowmom, cpart, njs, bars, head, npart);
+    launch_bwd_pair(st, md, wk, rowmom, cpart, nullptr, head, npart);
 }
 
 // Jacobian tape, once per rollout (off the critical path): sums, moments and records of ALL H steps in two launches --
@@ -1324,12 +1328,12 @@ void launch_mm_jac_finish(hipStream_t st, const MMModel& md, const MMWork& wk, i
     if (rlp) rl = *rlp;
     const int P = wk.PL, E = md.E, D = md.D;
     int njs, nrb;
-    mm_bwd_geometry(md.npad, md.E * (md.E + 1) / 2, &njs, &nrb);   // (the model's pairs, not this rank's: the split of a pair's sums is the same on every rank count)
+    mm_bwd_split(md.npad, md.E * (md.E + 1) / 2, wk.KP, &njs, &nrb);   // (the model's pairs, not this rank's: the split of a pair's sums is the same on every rank count)
     if (small_nch > 0) {   // the steps ran as one launch each (small_sweep): two blocks per chunk-workgroup, and the inverses are still to be made
         njs = 0;
         nrb = small_nch;
     }
-    const int nI = D * D, NS = mm_jac_ns(D);
+    const int nI = D * D;
     const int nrc = mm_bwd_rc(md.npad);
     BwdBatch bb;
     bb.gpart = (long)mm_jac_rowmom_size(md.npad, P);
@@ -1340,20 +1344,19 @@ void launch_mm_jac_finish(hipStream_t st, const MMModel& md, const MMWork& wk, i
     bb.in_m_stride = (long)tape_stride;
     double* mpart = part + (size_t)P * nrc * (1 + D + nI);
     if (small_nch > 0)
-        hipLaunchKernelGGL(k_mm_bwd_head, dim3(E + P, H), dim3(256), sizeof(double) * ((size_t)4 * nI + D), st, md, wk, head, bb.head, tape + D,
-                           (long)tape_stride);
-    const size_t lds_fin = sizeof(double) * std::max(std::max((size_t)4 * nI + 4 * D + 8, (size_t)3 * nI + NS + D + 2 * nI * D),
-                                                     rl.loc ? rev_local_lds_doubles(rl.E, rl.U) : (size_t)0);
+        launch_lds<k_mm_bwd_head>(dim3(E + P, H), dim3(256), sizeof(double) * head_lds(D).total, st, md, wk, head, bb.head, tape + D,
+                                  (long)tape_stride);
+    const size_t lds_fin = sizeof(double) * lds_launch_jac_fin(D, rl.loc != nullptr, rl.E, rl.U);
     const long jstride = (long)mm_jac_rec_size(D, E, P);
     {
         // the mean part's points in nrcm chunks per output and step: a workgroup's set-up and its epilogue (five tiles through
         // LDS, scattered stores) cost as much as four 64-point blocks -- 8 chunks of 2 blocks (the split finish's cut) spent
         // 22 us per workgroup at three per CU
         const int nrcm = std::max(1, std::min(2, md.npad / 64));
-        const size_t lds_rec = sizeof(double) * std::max((size_t)6 * 256 + (1 + D + nI) + 3 * nI + D + 2 + 1 + md.npad, (size_t)256 + 64 * 17 + 64 + 4 * 256 + 8 * JAC_MT + 2);
-        hipLaunchKernelGGL(k_mm_jac_rec, dim3(P + E * nrcm, H), dim3(256), lds_rec, st, md, wk, rowmom, cpart, njs, nrb, nrcm, head, mpart, jrec,
-                           jstride, bb);
-        hipLaunchKernelGGL(k_mm_jac_fin, dim3(E + (rl.loc ? 1 : 0), H), dim3(256), lds_fin, st, md, wk, part, nrcm, head, mpart, jrec, jstride, bb, P, rl);
+        const size_t lds_rec = sizeof(double) * lds_launch_jac_rec(D, md.npad);
+        launch_lds<k_mm_jac_rec>(dim3(P + E * nrcm, H), dim3(256), lds_rec, st, md, wk, rowmom, cpart, njs, nrb, nrcm, head, mpart, jrec,
+                                 jstride, bb);
+        launch_lds<k_mm_jac_fin>(dim3(E + (rl.loc ? 1 : 0), H), dim3(256), lds_fin, st, md, wk, part, nrcm, head, mpart, jrec, jstride, bb, P, rl);
     }
 }
 
@@ -1367,32 +1370,34 @@ void mm_bwd_geometry(int npad, int Pg, int* njs, int* nrb) {
     *njs = q;
 }
 
+// The split the sweep runs with: mm_bwd_geometry's, with more column splits (up to the 4 the buffers are sized for) where the
+// four column-sum slices would not fit the LDS beside the staging buffers and the kernel's static exp table (kp: the
+// contraction's rows, MMWork::KP).  With 47 or more pairs the geometry leaves the columns whole at npad = 4224, and one split
+// then needs 163 840 + 2 048 bytes of the 163 840 a workgroup can have: such a sweep could not be launched.  A split that fitted
+// is left as it is.
+void mm_bwd_split(int npad, int Pg, int kp, int* njs, int* nrb) {
+    mm_bwd_geometry(npad, Pg, njs, nrb);
+    while (2 * *njs <= 4 && sizeof(double) * sweep_lds(sweep_jws(npad, *njs), kp).total + SWEEP_STATIC_BYTES > LDS_MAX_BYTES) *njs *= 2;
+}
+
 void launch_mm_bwd(hipStream_t st, const MMModel& md, const MMWork& wk, double* rowmom, double* cpart, double* part,
                    const double* bars, double* head, double* out, unsigned* done, double* sum_out) {
     const int P = wk.PL, E = md.E, D = md.D;
-    int njs, nrb;
-    mm_bwd_geometry(md.npad, md.E * (md.E + 1) / 2, &njs, &nrb);   // (the model's pairs, not this rank's: the split of a pair's sums is the same on every rank count)
-    const int nhead = E + P, per_row = nrb * njs;
-    dim3 grid(nrb, P + (nhead + per_row - 1) / per_row, njs);   // the rows past P hold the head workgroups
-    const int LD = D | 1, nI = D * D;
-    const size_t lds_pair = sizeof(double) * std::max((size_t)4 * 16 * ((md.npad / 16 + njs - 1) / njs) + 2 * (BWD_CH * bwd_tp(wk.KP) + 2 * BWD_CH) + 4 * BWD_SCR_W, (size_t)4 * nI + D);
-    double* npart = nullptr;
-    launch_bwd_pair(st, grid, lds_pair, md, wk, rowmom, cpart, njs, bars, head, npart);
+    const SweepSplit sp = launch_bwd_pair(st, md, wk, rowmom, cpart, bars, head, nullptr);
+    const int njs = sp.njs, nrb = sp.nrb;
     const int nrc = mm_bwd_rc(md.npad);
-    double* mpart = part + (size_t)P * nrc * (1 + D + nI);
+    double* mpart = part + (size_t)P * nrc * (1 + D + D * D);
     const int nmt = (D + 16) / 16;
-    const size_t lds_post = sizeof(double) * std::max((size_t)2 * 256 * nmt * nmt + 4 * 256, (size_t)nI + 64 * LD + 128 + D + 2);
+    const size_t lds_post = sizeof(double) * lds_launch_bwd_post(D);
     const BwdBatch nob{0, 0, 0, 0, nullptr, 0};
 #define PPOST(NA_, M_)                                                                                                          \
-    hipLaunchKernelGGL((k_mm_bwd_post<NA_, M_>), dim3(P + E, nrc), dim3(256), lds_post, st, md, wk, rowmom, cpart, njs, nrb, part, nrc, \
-                       head, mpart, nob)
+    launch_lds<k_mm_bwd_post<NA_, M_>>(dim3(P + E, nrc), dim3(256), lds_post, st, md, wk, rowmom, cpart, njs, nrb, part, nrc, head, mpart, nob)
     if (D <= 14) PPOST(1, 1);
     else if (nmt == 1) PPOST(5, 1);
     else if (nmt == 2) PPOST(5, 2);
     else PPOST(5, 3);
 #undef PPOST
-    const size_t lds_fin = sizeof(double) * ((size_t)3 * nI + 4 * D + 8);
-    hipLaunchKernelGGL(k_mm_bwd_fin, dim3(P + E), dim3(256), lds_fin, st, md, wk, part, nrc, bars, head, mpart, out, done, sum_out);
+    launch_lds<k_mm_bwd_fin>(dim3(P + E), dim3(256), sizeof(double) * lds_launch_bwd_fin(D), st, md, wk, part, nrc, bars, head, mpart, out, done, sum_out);
 }
 int mm_bwd_rc(int npad) { return std::min(BWD_RC, npad / 64); }
 

@@ -3,8 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -98,6 +100,51 @@ __device__ __forceinline__ void kernarg_warm() {
                  : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(BYTES)
                  : "memory");
 #endif
+}
+
+inline int current_device() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    return dev;
+}
+// Compute units of a device (256, an MI355X's, if it cannot be asked), asked once per device (two threads that ask first at the
+// same time store the same number); device_cus(): of the current one.
+inline int device_cus_of(int device) {
+    static std::atomic<int> cached[64];
+    std::atomic<int>& slot = cached[device & 63];
+    int c = slot.load(std::memory_order_relaxed);
+    if (c == 0) {
+        hipDeviceProp_t prop;
+        c = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 256;
+        slot.store(c, std::memory_order_relaxed);
+    }
+    return c;
+}
+inline int device_cus() { return device_cus_of(current_device()); }
+
+// The launch of a kernel with dynamic LDS.  Up to LDS_DEFAULT_BYTES a launch needs no preparation; beyond that the function
+// must be opted in on the device it runs on (hipFuncAttributeMaxDynamicSharedMemorySize, a property of the function on ONE
+// device).  Per kernel K and device the largest size opted in so far is kept.  A launch above LDS_DEFAULT_BYTES asks for the
+// current device (a thread may have changed it since its last launch) and reads that mark without a lock; only a request above
+// the mark takes the mutex and sets the attribute -- a gradient group runs one host thread per context, possibly on several devices.
+constexpr size_t LDS_DEFAULT_BYTES = 48 * 1024;
+constexpr size_t LDS_MAX_BYTES = 160 * 1024;   // of a workgroup on gfx950
+template <auto K>
+inline void lds_opt_in(size_t lds) {
+    static std::mutex mu;
+    static std::atomic<size_t> mark[64];
+    std::atomic<size_t>& m = mark[current_device() & 63];
+    if (lds <= m.load(std::memory_order_acquire)) return;
+    std::lock_guard<std::mutex> lk(mu);
+    if (lds > m.load(std::memory_order_relaxed)) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        m.store(lds, std::memory_order_release);
+    }
+}
+template <auto K, typename... Args>
+inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+    if (lds > LDS_DEFAULT_BYTES) lds_opt_in<K>(lds);
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
 }
 
 // ---------------------------------------------------------------- linalg.hip

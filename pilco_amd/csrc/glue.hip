@@ -3,21 +3,19 @@
 
 namespace pilco {
 
-static size_t glue_lds_doubles(int E, int D, int SEG, int mp) {
-    const int nm = E > D ? E : D;
-    const size_t tail = (size_t)SEG + (size_t)mp;
-    const size_t rew = reward_lds_doubles(E);
-    return (size_t)3 * nm + 7 * (size_t)nm * nm + 256 + (tail > rew ? tail : rew);
-}
-size_t glue_lds_bytes(int E, int D) { return sizeof(double) * glue_lds_doubles(E, D, 0, 0); }
+// the link's LDS (doubles): what glue_lds_carve lays out -- carved here from an address that is never touched -- and the
+// inline RbfController's scratch behind it
 size_t glue_lds_doubles_for(const GlueArgs& g) {
-    int mp_n = (g.flags & GF_PACK) ? g.wk.EL * g.wk.NCHM * (1 + g.D) : 0;
-    int seg_n = (g.flags & (GF_PACK | GF_ASSEMBLE)) ? g.wk.SEG * ((g.flags & GF_PACK) ? 1 : g.wk.nranks) : 0;
-    if (g.flags & GF_RBF_POST) {
-        mp_n = g.pwk.EL * g.pwk.NCHM * (1 + g.E);
-        seg_n = g.pwk.SEG;
-    }
-    return glue_lds_doubles(g.E, g.D, seg_n, mp_n) + (((g.flags & GF_POLICY) && g.pol_inline) ? (size_t)g.pol_lds : 0);
+    double* const base = reinterpret_cast<double*>(uintptr_t{1} << 20);
+    GlueLds L;
+    glue_lds_carve(g, base, L);
+    return (size_t)(L.pol - base) + (((g.flags & GF_POLICY) && g.pol_inline) ? (size_t)g.pol_lds : 0);
+}
+size_t glue_lds_bytes(int E, int D) {   // a link that neither packs nor assembles
+    GlueArgs g{};
+    g.E = E;
+    g.D = D;
+    return sizeof(double) * glue_lds_doubles_for(g);
 }
 
 int rbf_inline_lds_doubles(int E, int U, int bf) { return link_rbf_inline_lds_doubles(E, U, bf); }
@@ -75,17 +73,7 @@ void launch_stamp(hipStream_t st, unsigned long long* dbg, int slot) {
 }
 
 void launch_glue(hipStream_t st, const GlueArgs& g, bool with_reward_block) {
-    const size_t lds = sizeof(double) * glue_lds_doubles_for(g);
-    static size_t configured[64] = {};   // per DEVICE: the attribute is a property of the function on one device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    size_t& conf = configured[dev & 63];
-    if (lds > conf) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_glue), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-        conf = lds;
-    }
-    hipLaunchKernelGGL(k_glue, dim3(with_reward_block ? 2 : 1), dim3(256), lds, st, g);
+    launch_lds<k_glue>(dim3(with_reward_block ? 2 : 1), dim3(256), sizeof(double) * glue_lds_doubles_for(g), st, g);
 }
 
 }  // namespace pilco

@@ -35,7 +35,9 @@ struct GlueLds {
     int o_sx, o_s1, o_js, o_seg, o_mp, o_misc;   // offsets (doubles) of sx, s1, js, seg, mp from mx, for multi_load
 };
 
-__device__ __forceinline__ void glue_lds_carve(const GlueArgs& g, double* sm, GlueLds& L) {
+// The link's LDS layout, for its two hosts and for the launchers (glue.hip: glue_lds_doubles_for measures it on the host): the
+// region ends at L.pol (+ GlueArgs::pol_lds doubles when the RbfController is evaluated inline).
+__host__ __device__ __forceinline__ void glue_lds_carve(const GlueArgs& g, double* sm, GlueLds& L) {
     const int E = g.E, D = g.D;
     const int nm = E > D ? E : D;
     int seg_n = (g.flags & (GF_PACK | GF_ASSEMBLE)) ? g.wk.SEG * ((g.flags & GF_PACK) ? 1 : g.wk.nranks) : 0;
@@ -57,7 +59,7 @@ __device__ __forceinline__ void glue_lds_carve(const GlueArgs& g, double* sm, Gl
         const int mp_n = (g.flags & GF_RBF_POST) ? g.pwk.EL * g.pwk.NCHM * (1 + E) : ((g.flags & GF_PACK) ? g.wk.EL * g.wk.NCHM * (1 + D) : 0);
         const int rew_n = (int)reward_lds_doubles(E);
         const int tail = seg_n + mp_n;
-        L.pol = L.seg + (tail > rew_n ? tail : rew_n);   // (matches glue_lds_doubles: the tail region is max(seg + mp, reward scratch))
+        L.pol = L.seg + (tail > rew_n ? tail : rew_n);   // (the tail region is max(seg + mp, reward scratch))
     }
     L.xm = nullptr;
     L.xs = nullptr;

@@ -3,6 +3,7 @@
 // chain's finish.  Host code only: the steps themselves are the rollout's (rollout.hip, with RolloutPlan::jrec set), the
 // records' kernels are bwd.hip's, the chain's rev.hip's; the host chains are grad.hip's.
 #include "ctx.h"
+#include "lds_layout.h"
 
 namespace {
 
@@ -41,7 +42,7 @@ int jtape_run(pilco_ctx* ctx, GradCall& gc, const double* m0, const double* S0, 
     ENSURE(s.jac_cpart, Hn * jb.cpart);
     ENSURE(s.jac_head, Hn * jb.head);
     ENSURE(s.jac_part, Hn * jb.part);
-    ENSURE(s.jac_np, (size_t)2 * std::max(P, 1) * mm_jac_nt(s.npad, s.wk.P));
+    ENSURE(s.jac_np, (size_t)2 * std::max(P, 1) * mm_jac_nt(s.npad, s.wk.P, s.wk.KP));
     ENSURE(ctx->tape, std::max<size_t>(1, (size_t)H * TS));
     ENSURE(ctx->jrec, std::max<size_t>(1, (size_t)H * JS));
     if (ctx->jpin_cap < pin_doubles) {

@@ -202,6 +202,7 @@ void launch_const_rows(hipStream_t st, double* a_row, int nA, double* b_row, int
 void launch_mm_bwd(hipStream_t st, const MMModel& md, const MMWork& wk, double* rowmom, double* cpart, double* part,
                    const double* bars, double* head, double* out, unsigned* done, double* sum_out);
 void mm_bwd_geometry(int npad, int Pg, int* njs, int* nrb);   // Pg: pairs of the whole model (rank-count independent split)
+void mm_bwd_split(int npad, int Pg, int kp, int* njs, int* nrb);   // ... made to fit the LDS: what the sweep runs with (kp = MMWork::KP)
 // Jacobian tape (bwd.hip).  Per step: launch_mm_sweep runs the reverse sweep in place of the forward pair kernel and
 // leaves rowmom / cpart / head in the step's own buffers (sizes below) and N_ab as npart [P][mm_jac_nt][2] tile partials
 // for the serial link; once per rollout launch_mm_jac_finish turns the H steps' buffers into the records
@@ -220,7 +221,7 @@ size_t mm_bwd_gpart_size(int npad, int P, int D);
 size_t mm_bwd_cpart_size(int npad, int P);
 size_t mm_jac_cpart_size(int npad, int P, int E);
 size_t mm_jac_head_size(int D, int E, int P);
-int mm_jac_nt(int npad, int Pg);
+int mm_jac_nt(int npad, int Pg, int kp);
 int mm_jac_ns(int D);
 int mm_bwd_rc(int npad);
 // The reverse chain of the policy gradient on the device (rev.hip).
@@ -248,13 +249,12 @@ struct RevArgs {
     const double* seeds;    // [H + 1][E + E*E] cotangent seeds of the caller's objective, or nullptr
     const double* Wp;       // LinearController W (U,E)
     const double* reward_dev;   // the rollout's reward on the device: handed out with the gradient (out[..]) instead of a copy of its own in front of the finish
-    double* amat;           // [H][rev_mat_doubles]: every step's reverse map [A; B] by columns | r | flags  (k_rev_step -> k_rev_chain)
+    double* amat;           // [H][rev_mat_doubles] (lds_layout.h): every step's reverse map [A; B] by columns | r | flags  (k_rev_step -> k_rev_chain)
     double* out;            // [rev_out(E, U).size] (grad_layout.h): dW | db | status (0 fine) | d / d (m_0, S_0 packed) | reward   (device-visible)
 };
 bool rev_chain_supported(int E, int U, int D);
 size_t rev_step_lds_bytes(int E, int U, int D);   // dynamic LDS of one k_rev_step workgroup
 size_t rev_loc_doubles(int E, int U);
-size_t rev_mat_doubles(int E, int U, int D);
 RevLocalArgs rev_local_args(int n, const RewardDev* rw, int E, int U, const double* traj, const double* Wp, const double* bp, const double* maxact,
                             double* loc);
 void launch_rev_chain(hipStream_t st, const RevArgs& a);

@@ -229,10 +229,7 @@ template <int KC, bool VSEP>
 static int sk_capacity_of() {
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_mm_pair_sk<KC, VSEP>, 256, 0) != hipSuccess || nb <= 0) nb = 2;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    return nb * cus * 4;
+    return nb * device_cus() * 4;
 }
 
 int mm_pair_sk_capacity(int KP, bool vsep, bool allow_env) {

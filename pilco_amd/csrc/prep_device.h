@@ -17,6 +17,19 @@ __host__ __device__ constexpr size_t prep_region_doubles(int DT) {   // the oper
     const size_t mean_blk = (size_t)2 * DT + 2 * (size_t)DT * DT + 4 + 9 * (size_t)(DT + 1) + 2 * (size_t)DT + 512 * (size_t)(DT + 2);
     return pair_blk > mean_blk ? pair_blk : mean_blk;
 }
+// The LDS of a k_mm_prep launch: the link's region first (fused head; link_doubles = 0: the plain operand kernel) -- an even
+// count of doubles, the region behind it is read with 16-byte accesses -- then the larger of the operand work's region with its
+// tail and the reward workgroup's (m | S | reward scratch for reward_E states; 0: no reward workgroup).
+struct PrepHeadLds {
+    int gd;         // doubles of the link's region = offset of the operand work's (k_mm_prep's glue_doubles)
+    size_t bytes;   // of the launch
+};
+inline PrepHeadLds prep_head_lds(int DT, size_t link_doubles, int reward_E) {
+    const size_t work = prep_region_doubles(DT) + PREP_TAB_DOUBLES;
+    const size_t rw = reward_E > 0 ? (size_t)reward_E + (size_t)reward_E * reward_E + reward_lds_doubles(reward_E) : 0;
+    const size_t gd = (link_doubles + 1) & ~(size_t)1;
+    return {(int)gd, sizeof(double) * ((work > rw ? work : rw) + gd)};
+}
 
 // 1 / l^2 of the w rows dealt to local pair pl (mm_device.h: wt_rows_per_pair), into the pair workgroup's `colbuf` [DT]
 template <int DT>

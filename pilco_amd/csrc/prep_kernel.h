@@ -12,7 +12,6 @@ namespace pilco {
 #ifndef PREP_PRE
 #define PREP_PRE 1   // the operand work's first phase is prepared BEFORE the link (0: A/B builds)
 #endif
-size_t prep_lds_bytes(int DT);
 
 // ------------------------------------------------------------------ prep
 // PK: the controller code compiled into the fused head's link (glue_body<PK, SR>): 0 none, 3 linear, 1 RBF from its own
@@ -94,9 +93,7 @@ __global__ __launch_bounds__(512, OCC2 ? 4 : 2) void k_mm_prep(MMModel md, MMWor
 struct PrepLaunch {
     hipStream_t st;
     dim3 grid;
-    size_t lds_rw;    // LDS bytes of the reward workgroup (0: none)
-    int gd;           // doubles of the link's LDS region (0: plain operand kernel)
-    int dev;
+    PrepHeadLds lds;
     bool fused, multi;
     int pk;
     const MMModel* md;
@@ -109,26 +106,14 @@ template <int DT>
 void launch_prep_dt(const PrepLaunch& a) {
     const hipStream_t st = a.st;
     const dim3 grid = a.grid;
-    const size_t lds_rw = a.lds_rw;
-    const int gd = a.gd, dev_ = a.dev, pk = a.pk;
+    const size_t lds = a.lds.bytes;
+    const int gd = a.lds.gd, pk = a.pk;
     const bool fused = a.fused, multi = a.multi;
     const MMModel& md = *a.md;
     const MMWork& wk = *a.wk;
     const PrepReward& r = *a.r;
     const GlueArgs& ga = *a.ga;
-#define PREP2(DT_, F_, PK_, SR_, O_)                                                                       \
-    do {                                                                                                   \
-        const size_t lds_ = std::max(prep_lds_bytes(DT_), lds_rw) + sizeof(double) * (size_t)gd;           \
-        static size_t configured_[64] = {};  /* beyond the default dynamic-LDS limit: opt in once PER DEVICE */ \
-        size_t& conf_ = configured_[dev_ & 63];                                                            \
-        if (conf_ == 0) conf_ = 48 * 1024;                                                                 \
-        if (lds_ > conf_) {                                                                                \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_mm_prep<DT_, F_, PK_, SR_, O_>),     \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_);              \
-            conf_ = lds_;                                                                                  \
-        }                                                                                                  \
-        hipLaunchKernelGGL((k_mm_prep<DT_, F_, PK_, SR_, O_>), grid, dim3(512), lds_, st, md, wk, r, ga, gd); \
-    } while (0)
+#define PREP2(DT_, F_, PK_, SR_, O_) launch_lds<k_mm_prep<DT_, F_, PK_, SR_, O_>>(grid, dim3(512), lds, st, md, wk, r, ga, gd)
     /* the two-per-CU build exists for the single-rank heads with a controller at DT <= 8 (the lanes of a gradient batch) */
 #define PREP1(DT_, F_, PK_, SR_)                                                                           \
     do {                                                                                                   \

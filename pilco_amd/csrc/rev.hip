@@ -13,7 +13,7 @@
 //   k_rev_chain   ONE workgroup walks t = H-1 .. 0: a matrix-vector product per step, gradient accumulators in registers.
 // Fixed summation orders throughout: the gradient is bitwise repeatable, and identical on every rank of a sharded model
 // (every rank runs the same chain over the same all-gathered records).
-#include "grad_layout.h"
+#include "lds_layout.h"
 #include "rev_local.h"
 
 namespace pilco {
@@ -29,12 +29,8 @@ namespace pilco {
 // 77 x 65 map x -> (mbar_joint | sbar_joint), pushes the 65 basis cotangents through joint Gaussian, squash and controller
 // (pilco.py:141-144, controllers.py:13-58) and leaves [A_t; B_t] (76 x 65, stored by columns) and r_t; what remains
 // sequential is one 40 kB matrix-vector product per step with two barriers (k_rev_chain).
-// (the dimensions NX, NP, NR, .. and the records' recp / reco: RevDims, grad_layout.h)
-constexpr int REVS_SPLIT = 4;   // workgroups per step of k_rev_step (column ranges of [A; B]); a flag each
-size_t rev_mat_doubles(int E, int U, int D) {   // per step: [A; B] by columns | r | flags
-    const RevDims d = rev_dims(E, U, D);
-    return (size_t)d.NX * d.NR + d.NX + REVS_SPLIT;
-}
+// (the dimensions NX, NP, NR, .. and the records' recp / reco: RevDims, grad_layout.h; REVS_SPLIT workgroups per step, the map's
+// size per step rev_mat_doubles and the two kernels' LDS: lds_layout.h)
 __device__ __forceinline__ int rev_tri(int r, int c) { return r <= c ? c * (c + 1) / 2 + r : r * (r + 1) / 2 + c; }   // packed symmetric index
 // pair index of (r, c) in the dealing order (diagonal first)
 __device__ __forceinline__ int rev_pair(int E, int r, int c) {
@@ -45,12 +41,6 @@ __device__ __forceinline__ int rev_pair(int E, int r, int c) {
 
 constexpr int REVS_NT = 1024;   // threads of a k_rev_step workgroup
 constexpr int REV_MAXU = 4;
-// LDS of k_rev_step (doubles): M1 [NX][NOUT] | s1 (E,D) | M (E) | V (D,E) | m_x | s_x | loc | W | gcol [NX][U + U*U] | pab (ints)
-__host__ __device__ inline size_t rev_step_lds_doubles(int E, int U, int D) {
-    const RevDims d = rev_dims(E, U, D);
-    return (size_t)d.NX * d.NOUT + 2 * (size_t)E * D + E + (size_t)E + (size_t)E * E + rev_loc_size(E, U) + (size_t)U * E +
-           (size_t)d.NX * (U + U * U) + (size_t)(d.P + 1) / 2 + 2;
-}
 
 __global__ __launch_bounds__(REVS_NT) void k_rev_step(RevArgs a) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -61,16 +51,17 @@ __global__ __launch_bounds__(REVS_NT) void k_rev_step(RevArgs a) {
     // this workgroup's columns of [A; B] = rows of M1 (REVS_SPLIT workgroups per step: one workgroup per step was 42 us -- 10 of
     // set-up, 11 fold, 20 matrix entries -- on 40 of 256 CUs; every part stages the step's small data, folds into and reads its own rows only)
     const int c0 = (int)((long)part * NX / REVS_SPLIT), c1 = (int)((long)(part + 1) * NX / REVS_SPLIT);
-    double* M1 = sm;                    // [NX][NOUT]: row a < E: d (mbar_j | sbar_j) / d mbar_a, row E + p: d / d sbar_p
-    double* s1 = M1 + (size_t)NX * NOUT;
-    double* Mg = s1 + ED;
-    double* Vg = Mg + E;
-    double* mx = Vg + ED;
-    double* sx = mx + E;
-    double* loc = sx + E * E;           // rg (E + E*E) | T1 | T2 | sqM | sqCd | sqS | q | Ep | Em | cdm | csm | sdm | ssm | ee
-    double* Wl = loc + NLOC;
-    double* gcol = Wl + UE;             // [NX][U + UU]: mu0bar | su0bar of every basis column
-    int* pab = (int*)(gcol + (size_t)NX * GC);
+    const RevStepLds L = rev_step_lds(E, U, D);
+    double* M1 = sm + L.M1;             // [NX][NOUT]: row a < E: d (mbar_j | sbar_j) / d mbar_a, row E + p: d / d sbar_p
+    double* s1 = sm + L.s1;
+    double* Mg = sm + L.Mg;
+    double* Vg = sm + L.Vg;
+    double* mx = sm + L.mx;
+    double* sx = sm + L.sx;
+    double* loc = sm + L.loc;           // rg (E + E*E) | T1 | T2 | sqM | sqCd | sqS | q | Ep | Em | cdm | csm | sdm | ssm | ee
+    double* Wl = sm + L.Wl;
+    double* gcol = sm + L.gcol;         // [NX][U + UU]: mu0bar | su0bar of every basis column
+    int* pab = (int*)(sm + L.pab);
     const double* rg = loc;
     const double* T1 = loc + SE;
     const double* T2 = T1 + UE;
@@ -192,7 +183,7 @@ __global__ __launch_bounds__(REVS_NT) void k_rev_step(RevArgs a) {
         if (!(fabs(rg[i]) <= 1.7e308)) bad = true;       // singular I + S W in a reward term
     const int anybad = __syncthreads_or(bad ? 1 : 0);
     // ---- 3: the entries of [A; B], column by column (stored by columns: the chain's lanes run along the rows)
-    double* AT = a.amat + (long)t * ((long)NX * NR + NX + REVS_SPLIT);
+    double* AT = a.amat + (long)t * (long)rev_mat_doubles(E, U, D);
     for (int i = c0 * NR + tid; i < c1 * NR; i += REVS_NT) {
         const int col = i / NR, row = i - col * NR;
         const double* am = M1 + (size_t)col * NOUT;
@@ -246,7 +237,7 @@ __global__ __launch_bounds__(REVS_NT) void k_rev_step(RevArgs a) {
 }
 
 // ------------------------------------------------------------------ the chain: x_t = A_t x_{t+1} + r_t (+ seeds), dtheta += B_t x_{t+1}
-constexpr int REV_NT = 512;   // threads of the chain's workgroup
+// (REV_NT threads: lds_layout.h)
 constexpr int REV_RT = 16;    // matrix entries a thread keeps in flight for the NEXT step (registers)
 // LDS-only barrier: the workgroup's global loads in flight (the next step's matrix) are NOT waited for
 __device__ __forceinline__ void rev_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -256,10 +247,11 @@ __global__ __launch_bounds__(REV_NT) void k_rev_chain(RevArgs a) {
     const int tid = threadIdx.x;
     const RevDims dm = rev_dims(a.E, a.U, a.D);
     const int E = dm.E, H = a.H, NX = dm.NX, NR = dm.NR, SE = E + E * E;
-    const int NCH = REV_NT / NR, nper = (NX + NCH - 1) / NCH;   // thread (chunk c_, row): columns c_ * nper ..
-    const long MS = (long)NX * NR + NX + REVS_SPLIT;
-    double* x = sm;                 // [NX] (+ one zero behind it: the coefficient of a slot past a thread's share)
-    double* part = x + NX + 1;      // [NCH][NR]
+    const RevChainLds L = rev_chain_lds(a.E, a.U, a.D);
+    const int NCH = L.nch, nper = (NX + NCH - 1) / NCH;   // thread (chunk c_, row): columns c_ * nper ..
+    const long MS = (long)rev_mat_doubles(a.E, a.U, a.D);
+    double* x = sm + L.x;           // [NX] (+ one zero behind it: the coefficient of a slot past a thread's share)
+    double* part = sm + L.part;     // [NCH][NR]
     const int c_ = tid / NR, row = tid - c_ * NR;
     const bool mv = c_ < NCH;
     const int k0 = c_ * nper, nok = mv ? max(0, min(nper, NX - k0)) : 0;
@@ -347,27 +339,17 @@ __global__ __launch_bounds__(REV_NT) void k_rev_chain(RevArgs a) {
 }
 
 void launch_rev_chain(hipStream_t st, const RevArgs& a) {
-    if (a.H > 0) {
-        const size_t lds_s = sizeof(double) * rev_step_lds_doubles(a.E, a.U, a.D);
-        static size_t lds_set = 0;
-        if (lds_s > 65536 && lds_s > lds_set) {
-            (void)hipFuncSetAttribute((const void*)k_rev_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-            lds_set = lds_s;
-        }
-        hipLaunchKernelGGL(k_rev_step, dim3(a.H, REVS_SPLIT), dim3(REVS_NT), lds_s, st, a);
-    }
-    const RevDims d = rev_dims(a.E, a.U, a.D);
-    const size_t lds = sizeof(double) * ((size_t)d.NX + 1 + (size_t)(REV_NT / d.NR) * d.NR);
-    hipLaunchKernelGGL(k_rev_chain, dim3(1), dim3(REV_NT), lds, st, a);
+    if (a.H > 0) launch_lds<k_rev_step>(dim3(a.H, REVS_SPLIT), dim3(REVS_NT), rev_step_lds_bytes(a.E, a.U, a.D), st, a);
+    launch_lds<k_rev_chain>(dim3(1), dim3(REV_NT), sizeof(double) * rev_chain_lds(a.E, a.U, a.D).total, st, a);
 }
 
 bool rev_chain_supported(int E, int U, int D) {
     const RevDims d = rev_dims(E, U, D);
     return U > 0 && U <= REV_MAXU && D == E + U && D <= 14 && d.NR <= REV_NT && d.P < 65536 &&
-           sizeof(double) * rev_step_lds_doubles(E, U, D) <= 160 * 1024;
+           rev_step_lds_bytes(E, U, D) <= LDS_MAX_BYTES;
 }
 
-size_t rev_step_lds_bytes(int E, int U, int D) { return sizeof(double) * rev_step_lds_doubles(E, U, D); }
+size_t rev_step_lds_bytes(int E, int U, int D) { return sizeof(double) * (size_t)rev_step_lds(E, U, D).total; }
 size_t rev_loc_doubles(int E, int U) { return (size_t)rev_loc_size(E, U); }
 RevLocalArgs rev_local_args(int n, const RewardDev* rw, int E, int U, const double* traj, const double* Wp, const double* bp, const double* maxact,
                             double* loc) {

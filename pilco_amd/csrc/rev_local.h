@@ -1,6 +1,7 @@
 // Trajectory-only quantities of one step of the policy gradient's reverse chain (included by rev.hip, whose k_rev_local runs it
 // as a launch of its own, and by bwd.hip, where it rides as an extra workgroup per step in the records' last launch).
 #pragma once
+#include "lds_layout.h"
 #include "mm_device.h"
 
 namespace pilco {
@@ -11,20 +12,21 @@ namespace pilco {
 // loc [H][rev_loc_size]: (d mu / d m | d mu / d S) | T1 = W s_x^T (U,E) | T2 = W s_x (U,E) | squash_sin forward (controllers.py:
 // 13-36): M (U) | Cd (U) | S | q | Ep | Em | cos(dm) | cos(sm) | sin(dm) | sin(sm) | e_u e_v (U,U each) -- the order the chain
 // keeps them in LDS.  A singular I + S W leaves non-finite entries in the first block (the chain reports it).
-__host__ __device__ inline int rev_loc_size(int E, int U) { return E + E * E + 2 * U * E + 2 * U + 9 * U * U; }
+// (its size: rev_loc_size, lds_layout.h)
 __device__ inline void rev_local_step(int n, const RevRewards& rs, int E, int U, const double* __restrict__ traj, const double* __restrict__ Wp,
                                       const double* __restrict__ bp, const double* __restrict__ maxact, double* __restrict__ loc, int z,
                                       double* sm) {
     const int t = threadIdx.x, SE = E + E * E, nc = 2 * E, NLOC = rev_loc_size(E, U);
-    double* mx = sm;               // [E] | sx [E][E]
-    double* sx = mx + E;
-    double* dm = sx + E * E;       // [E] | dS [E][E]
-    double* dS = dm + E;
-    double* v = dS + E * E;        // [E]  X d
-    double* dTi = v + E;           // [E]  d^T X
-    double* d = dTi + E;           // [E]
-    double* G0 = d + E;            // [E][2E]
-    double* G1 = G0 + E * nc;      // [E][2E]
+    const RevLocalLds L = rev_local_lds(E, U);
+    double* mx = sm + L.mx;        // [E] | sx [E][E]
+    double* sx = sm + L.sx;
+    double* dm = sm + L.dm;        // [E] | dS [E][E]
+    double* dS = sm + L.dS;
+    double* v = sm + L.v;          // [E]  X d
+    double* dTi = sm + L.dTi;      // [E]  d^T X
+    double* d = sm + L.d;          // [E]
+    double* G0 = sm + L.G0;        // [E][2E]
+    double* G1 = sm + L.G1;        // [E][2E]
     for (int e = t; e < SE; e += 256) {
         mx[e] = traj[(long)z * SE + e];
         dm[e] = 0.0;
@@ -131,11 +133,6 @@ __device__ inline void rev_local_step(int n, const RevRewards& rs, int E, int U,
             q0[U + u] = maxact[u] * ex * cos(mu0[u]);
         }
     }
-}
-
-__host__ __device__ inline size_t rev_local_lds_doubles(int E, int U) {
-    const size_t gj = (size_t)4 * E * E, pol = (size_t)2 * U * E + U;
-    return (size_t)2 * (E + E * E) + 3 * E + (gj > pol ? gj : pol) + 8;
 }
 
 }  // namespace pilco

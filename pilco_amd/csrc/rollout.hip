@@ -138,15 +138,6 @@ static int xq_begin(pilco_ctx* ctx) {
     return PILCO_OK;
 }
 
-static int device_cus_of(int device) {
-    static int cached[64] = {};
-    int& c = cached[device & 63];
-    if (c == 0) {
-        hipDeviceProp_t prop;
-        c = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
-    return c;
-}
 // Column splits of the one-launch small step (MMWork::NCS): with 64-row workgroups whose operands stay in LDS, a pair's
 // columns are dealt over up to four workgroups as long as the whole launch stays ONE round of the chip (one workgroup per
 // CU) -- a small model with few outputs would otherwise leave most CUs idle while 40 of them work through the pair sums.
@@ -509,7 +500,7 @@ static int enqueue_rollout_steps(pilco_ctx* ctx, const RolloutPlan& plan, int H)
     g.s_out = nullptr;
     if (plan.jrec) {   // Jacobian tape (bwd.hip): the serial link packs N_ab from the per-workgroup partials the reverse sweep
         g.wk.sk_waves = 0;   // leaves in the tile-partial layout
-        g.wk.NT = mm_jac_nt(s.npad, s.wk.P);
+        g.wk.NT = mm_jac_nt(s.npad, s.wk.P, s.wk.KP);
         g.wk.pair_part = s.jac_np.p;
     }
     switch (plan.route.step) {

@@ -232,6 +232,69 @@ def test_policy_gradients_vs_autograd(case):
         cx.close()
 
 
+def test_jacobian_tape_where_the_record_kernel_asks_for_more_than_64_kb():
+    """E = 1, U = 1 (D = 2), N = 6600 (npad = 6656), H = 2: the smallest shape at which k_mm_jac_rec's dynamic LDS -- 6 x 256 +
+    (1 + D + D^2) + 3 D^2 + D + 2 + 1 + npad doubles, 65 728 bytes -- is above the 64 KB a launch gets without opting in (the
+    sweep is at 80 KB there).  Value and gradient on the Jacobian tape against the plain tape of the same context at TOL_GRAD,
+    the bound both routes are held to against autograd at the sizes where autograd can be run."""
+    assert 8 * (6 * 256 + (1 + 2 + 4) + 3 * 4 + 2 + 2 + 1 + 6656) == 65728 > 65536 >= 8 * (6 * 256 + 7 + 12 + 4 + 1 + 6592)
+    case = nc._c("n6600_rec64k", 6600, 1, 1, H=2)
+    d = nc.make_data(case)
+    cx = _context(case, d)
+    try:
+        pol, rw = _policy(case, d), _rewards(case, d)
+        _settings(cx)
+        g = _grad_call(cx, case, d, pol, rw)
+        rt = cx.last_route()
+        assert rt["entry"] == 2 and rt["tape"] == 2 and rt["pair"] == 4 and rt["npad"] == 6656 and rt["H"] == 2, rt
+        _settings(cx, grad_mode=0)
+        p = _grad_call(cx, case, d, pol, rw)
+        rp = cx.last_route()
+        assert rp["entry"] == 2 and rp["tape"] == 1 and rp["npad"] == 6656, rp
+        for x in list(g) + list(p):
+            assert np.all(np.isfinite(np.asarray(x, dtype=np.float64))), "non-finite result"
+        errs = [abs(g[0] - p[0]) / abs(p[0])] + [wr.block_error(np.asarray(x).reshape(np.shape(y)), np.asarray(y)) for x, y in zip(g[1:], p[1:])]
+        print("n6600_rec64k: Jacobian tape vs plain tape, reward / gradient blocks %s" % ["%.2e" % e for e in errs])
+        _note(case["name"], "jac_vs_plain", max(errs))
+        assert max(errs) <= nc.TOL_GRAD, "reward / gradient blocks %s (tol %.0e)" % (["%.2e" % e for e in errs], nc.TOL_GRAD)
+    finally:
+        cx.close()
+
+
+def test_jacobian_tape_where_the_sweep_needs_a_further_column_split():
+    """E = 10, U = 1 (D = 11, 55 pairs), N = 4200 (npad = 4224), H = 2: mm_bwd_geometry leaves the columns whole (33 row blocks x
+    55 pairs >= 1536), and this is the smallest npad at which the sweep's workgroup with one split -- 8 (4 x 4224 + 2 x 1216 +
+    1152) = 163 840 dynamic bytes and the 2 048 of its exp table -- is above the 163 840 a workgroup can have; mm_bwd_split runs
+    it with two.  The Jacobian tape against the plain tape at TOL_GRAD as above; both take their value from the sweep, so the
+    reward is also held to the forward rollout's (the pair kernel's sums): each is held to the oracle at TOL_FWD where the oracle
+    can be run, hence 2 TOL_FWD between them."""
+    assert 8 * (4 * 4224 + 2 * 1216 + 1152) + 2048 > 160 * 1024 >= 8 * (4 * 4160 + 2 * 1216 + 1152) + 2048 and nc.bwd_geometry(4224, 55) == (1, 33)
+    case = nc._c("n4200_split", 4200, 10, 1, H=2)
+    d = nc.make_data(case)
+    cx = _context(case, d)
+    try:
+        pol, rw = _policy(case, d), _rewards(case, d)
+        _settings(cx)
+        fwd = cx.rollout(pol, rw, d["m0"], d["S0"], case["H"])
+        r_fwd = float(np.asarray(fwd[2]).ravel()[0])
+        g = _grad_call(cx, case, d, pol, rw)
+        rt = cx.last_route()
+        assert rt["entry"] == 2 and rt["tape"] == 2 and rt["pair"] == 4 and rt["npad"] == 4224, rt
+        _settings(cx, grad_mode=0)
+        p = _grad_call(cx, case, d, pol, rw)
+        assert cx.last_route()["tape"] == 1
+        for x in list(g) + list(p):
+            assert np.all(np.isfinite(np.asarray(x, dtype=np.float64))), "non-finite result"
+        errs = [abs(g[0] - p[0]) / abs(p[0])] + [wr.block_error(np.asarray(x).reshape(np.shape(y)), np.asarray(y)) for x, y in zip(g[1:], p[1:])]
+        rerr = max(abs(g[0] - r_fwd), abs(p[0] - r_fwd)) / abs(r_fwd)
+        print("n4200_split: Jacobian tape vs plain tape %s, reward vs the forward rollout %.2e" % (["%.2e" % e for e in errs], rerr))
+        _note(case["name"], "jac_vs_plain", max(errs))
+        assert max(errs) <= nc.TOL_GRAD, "reward / gradient blocks %s (tol %.0e)" % (["%.2e" % e for e in errs], nc.TOL_GRAD)
+        assert rerr <= 2 * nc.TOL_FWD, "reward against the forward rollout %.2e" % rerr
+    finally:
+        cx.close()
+
+
 _LANE_CASES = [c for c in nc.CASES if c["lanes"]]
 
 
