@@ -13,7 +13,11 @@ noise) without the gym base class.  What this example exercises beyond inverted_
 policy gradient of an objective that is NOT only the additive reward (the risk term's cotangent seeds in the native reverse
 sweep, pilco_rollout_grad_rbf_seeded), a fixed (non-trainable) likelihood variance, and `pilco.mu` as a Parameter.
 
-    python examples/safe_cars.py [--iters N]
+    python examples/safe_cars.py [--iters N] [--particle-risk [P]]
+
+--particle-risk: after the last iteration, SafePILCO.sample_risk -- the risk the optimiser saw (moment matching, the Normal
+scale and the independence across steps as the reference writes them) beside the fraction of P particles of the learned
+dynamics that are inside the junction, per step and at least once within the horizon (docs/particles.md).
 """
 import argparse
 import os
@@ -81,7 +85,7 @@ def rollout(env, action_fn, timesteps):
     return np.stack(X), np.stack(Y), ret
 
 
-def run(iters=5, seed=0, verbose=True):
+def run(iters=5, seed=0, verbose=True, particle_risk=0):
     from pilco_amd.controllers import RbfController
     from pilco_amd.params import set_trainable
     from pilco_amd.rewards import LinearReward
@@ -140,12 +144,24 @@ def run(iters=5, seed=0, verbose=True):
             print("[safe cars] iteration %d: optimize_models %.2f s  optimize_policy(maxiter=20, restarts=2) %.2f s  predicted return %.2f  "
                   "predicted risk %.3g (mu %.0f)  plant return %+.0f  both cars in the junction at once: %s"
                   % (it, t1 - t0, t2 - t1, rewards.sum(), overall, mu_before, ret, crossed))
-    return dict(total_s=time.perf_counter() - t_all, iterations=stages)
+    out = dict(total_s=time.perf_counter() - t_all, iterations=stages)
+    if particle_risk:
+        r = pilco.sample_risk(m_init, S_init, T, num_particles=int(particle_risk), seed=seed)
+        out["risk_sample"] = r
+        if verbose:
+            with np.printoptions(precision=3, suppress=True):
+                print("[safe cars] risk per step, moment matching:", r.risk_moment_matched)
+                print("[safe cars] risk per step, %d particles:  " % int(particle_risk), r.risk_particles)
+            print("[safe cars] in the junction at least once within %d steps: moment matching %.3g, particles %.3g"
+                  % (T, r.any_hit_moment_matched, r.any_hit_particles))
+    return out
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--particle-risk", type=int, nargs="?", const=1000, default=0, metavar="P",
+                    help="after the last iteration print the moment-matched risk beside the risk on P particles (default 1000)")
     a = ap.parse_args()
-    out = run(iters=a.iters)
+    out = run(iters=a.iters, particle_risk=a.particle_risk)
     print("Safe-PILCO, linear cars, HIP path: total wall-clock %.2f s" % out["total_s"])

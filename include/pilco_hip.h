@@ -193,6 +193,28 @@ int pilco_reward_eval(pilco_ctx* ctx, const pilco_reward_term* rewards, int n_re
 int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
                             const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
                             double* mean, double* cov, double* reward_steps, double* particles, double* eps_out);
+/* Constraint events on the particles (extension; docs/particles.md): an event is a box over a few state coordinates, or the
+ * complement of one.  inside(x): every clause holds, low <= x[dim] && x[dim] <= high (closed intervals; -INFINITY /
+ * +INFINITY: no bound on that side).  hit(x) = complement ? !inside(x) : inside(x).  A NaN coordinate fails its clause:
+ * inside is false and hit equals complement.  The predicate itself is csrc/particle_events.h (host and device).
+ * Safe-PILCO's RiskOfCollision(state_dim, low, high) is two clauses, on dims 0 and 2; SingleConstraint(dim, high, low,
+ * inside) is one clause with complement = !inside. */
+#define PILCO_MAX_EVENTS 8
+#define PILCO_MAX_EVENT_CLAUSES 4
+typedef struct pilco_event_clause { int dim; double low, high; } pilco_event_clause;   /* -INFINITY / +INFINITY: no bound on that side */
+typedef struct pilco_event { int n_clauses; int complement; pilco_event_clause clause[PILCO_MAX_EVENT_CLAUSES]; } pilco_event;
+/* pilco_rollout_particles with events counted on the device: the same arguments in the same order, the same launches and
+ * the same output bits, and behind the statistics of every state t = 0..H (row 0 = x0) two counting launches over all
+ * particles of the step.  counts (H+1, n_events): the number of particles with hit at state t.  first_hit (P, n_events),
+ * may be NULL: the smallest t in 0..H at which particle p hits event k, or -1.  Integer results: blocks of 128 particles
+ * count by wave ballot, the blocks' counts are added in block order; no atomics.  Both arrive with the call's one download.
+ * n_events = 0 is pilco_rollout_particles itself.  PILCO_E_SHAPE, before any launch or upload, for n_events outside
+ * 0..PILCO_MAX_EVENTS, n_events > 0 with a null events or counts, n_clauses outside 1..PILCO_MAX_EVENT_CLAUSES, a dim
+ * outside [0, E), a NaN bound or low > high; and for everything pilco_rollout_particles refuses. */
+int pilco_rollout_particles_events(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                   const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                   int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
+                                   double* eps_out, const pilco_event* events, int n_events, long long* counts, int* first_hit);
 
 /* ------------------------------------------------------------------ reverse mode
  * The reference differentiates training_loss with TensorFlow's autodiff (pilco/models/pilco.py:85-90);

@@ -20,6 +20,7 @@ STATUS_NAMES = {1: "PILCO_E_SHAPE", 2: "PILCO_E_NOT_PD", 3: "PILCO_E_HIP", 4: "P
 SLOT_DYNAMICS, SLOT_POLICY = 0, 1
 POLICY_NONE, POLICY_LINEAR, POLICY_RBF = 0, 1, 2
 REWARD_EXPONENTIAL, REWARD_LINEAR = 1, 2
+MAX_EVENTS, MAX_EVENT_CLAUSES = 8, 4
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 64
 
@@ -43,6 +44,23 @@ class PolicyStruct(C.Structure):
 
 class RewardTerm(C.Structure):
     _fields_ = [("kind", C.c_int), ("coef", C.c_double), ("W", _dp), ("t", _dp)]
+
+
+class EventClause(C.Structure):
+    _fields_ = [("dim", C.c_int), ("low", C.c_double), ("high", C.c_double)]
+
+
+class Event(C.Structure):
+    _fields_ = [("n_clauses", C.c_int), ("complement", C.c_int), ("clause", EventClause * MAX_EVENT_CLAUSES)]
+
+
+def event_spec_of(ev):
+    """An event as the dict the binding takes: dict(clauses=[(dim, low, high), ...], complement=bool), a bound of None meaning
+    no bound on that side.  ev: such a dict, or an object with event_spec() (pilco_amd.safe's constraints)."""
+    spec = ev.event_spec() if hasattr(ev, "event_spec") else ev
+    if not isinstance(spec, dict) or "clauses" not in spec:
+        raise TypeError("an event is a dict(clauses=[(dim, low, high), ...], complement=bool) or offers event_spec()")
+    return spec
 
 
 # every symbol include/pilco_hip.h declares: name -> (restype, argtypes)
@@ -80,6 +98,9 @@ SIGNATURES = {
                                 _dp, _dp, _dp, _dp]),
     "pilco_rollout_particles": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
                                           _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles_events": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                                 _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp,
+                                                 C.POINTER(Event), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "pilco_gp_predict_vjp": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout_tape": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                      _dp, _dp, _dp, _dp, _dp]),
@@ -408,10 +429,31 @@ class Context:
             return mH, SH, rew, traj
         return mH, SH, rew
 
-    def rollout_particles(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_particles=False):
+    @staticmethod
+    def _events(events):
+        """events: list of event dicts / objects with event_spec() -> a ctypes array of pilco_event."""
+        arr = (Event * max(len(events), 1))()
+        for k, ev in enumerate(events):
+            spec = event_spec_of(ev)
+            clauses = list(spec["clauses"])
+            if len(clauses) > MAX_EVENT_CLAUSES:
+                raise ValueError(f"an event has at most {MAX_EVENT_CLAUSES} clauses")
+            arr[k].n_clauses = len(clauses)
+            arr[k].complement = 1 if spec.get("complement", False) else 0
+            for j, (dim, low, high) in enumerate(clauses):
+                arr[k].clause[j].dim = int(dim)
+                arr[k].clause[j].low = -np.inf if low is None else float(low)
+                arr[k].clause[j].high = np.inf if high is None else float(high)
+        return arr
+
+    def rollout_particles(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_particles=False,
+                          events=None):
         """P sampled trajectories of H steps through the learned dynamics, on the device (pilco_rollout_particles):
         x0 (P, E) initial particles; eps (H, P, E) standard-normal draws, or None: generated on the device from ``seed``.
-        Returns mean (H+1, E), cov (H+1, E, E), reward_steps (H,), particles (H+1, P, E) or None, the draws used (H, P, E)."""
+        Returns mean (H+1, E), cov (H+1, E, E), reward_steps (H,), particles (H+1, P, E) or None, the draws used (H, P, E).
+        events (a list of K event dicts, see event_spec_of; pilco_rollout_particles_events): two more results follow, counts
+        (H+1, K) int64 -- the number of particles that hit event k at state t -- and first_hit (P, K) int32, the first such
+        t of every particle or -1."""
         E = policy["state_dim"]
         p, k1 = self._policy(policy)
         r, k2 = self._rewards(rewards, E)
@@ -428,10 +470,19 @@ class Context:
         rew = np.empty((max(H, 0),))
         parts = np.empty((H + 1, P, E)) if want_particles else None
         used = np.empty((H, P, E))
-        self._chk(self.lib.pilco_rollout_particles(self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps),
-                                                   C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), 1 if observation_noise else 0,
-                                                   _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used)))
-        return mean, cov, rew, parts, used
+        args = (self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                1 if observation_noise else 0, _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used))
+        if events is None:
+            self._chk(self.lib.pilco_rollout_particles(*args))
+            return mean, cov, rew, parts, used
+        events = list(events)
+        K = len(events)
+        ev = self._events(events)
+        counts = np.zeros((H + 1, K), np.int64)
+        first = np.full((P, K), -1, np.int32)
+        self._chk(self.lib.pilco_rollout_particles_events(*args, ev, K, counts.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                          first.ctypes.data_as(C.POINTER(C.c_int))))
+        return mean, cov, rew, parts, used, counts, first
 
     def particle_actions(self, policy, x):
         """Test aid: the actions (P, U) the particle rollout acts with at the states x (P, E) (pilco_debug_particle_actions)."""

@@ -16,6 +16,12 @@
 // cancellation against |x|^2): S1_a = sum (x_a - c_a), S2_ab = sum (x_a - c_a)(x_b - c_b);
 //   mean_a = c_a + S1_a / P,   cov_ab = S2_ab / P - (S1_a / P)(S1_b / P),   reward = (sum r_p) / P.
 // The same particles in the same order give the same bits, whatever P is chunked into; P = 1 gives a zero covariance exactly.
+//
+// EVENTS (pilco_rollout_particles_events; the predicate: particle_events.h).  Behind the statistics of every state t = 0..H,
+// over all particles of the step:
+//   k_particle_events / k_particle_events_finish   per event the number of particles that hit it, and every particle's first hit
+// Integer counts: a block of PT_BLOCK particles counts by wave ballot, the blocks' counts are added in block order; no atomics.
+#include "particle_events.h"
 #include "philox_normal.h"
 #include "predict.h"
 
@@ -189,6 +195,45 @@ __global__ __launch_bounds__(PT_BLOCK) void k_particle_finish(ParticleStatArgs a
     }
 }
 
+struct ParticleEventArgs {
+    const double* x;     // [P][E] the states after t steps
+    int* first_hit;      // [P][K] the first t with a hit, -1 so far; or nullptr
+    int* part;           // [nblk][K] the blocks' counts
+    long long* counts;   // [K] row t of the counts
+    int P, E, K, t, nblk;
+    pilco_event ev[PILCO_MAX_EVENTS];   // the table travels in the kernel arguments (832 bytes)
+};
+
+// block b: particles PT_BLOCK b .. , one thread per particle; a wave counts its hits by ballot, thread k adds the two waves
+__global__ __launch_bounds__(PT_BLOCK) void k_particle_events(ParticleEventArgs a) {
+    __shared__ int wave_hits[PT_BLOCK / 64][PILCO_MAX_EVENTS];
+    const int i = threadIdx.x, K = a.K;
+    const long p = (long)blockIdx.x * PT_BLOCK + i;
+    const bool live = p < a.P;
+    const double* xr = a.x + (live ? p : 0) * a.E;
+    for (int k = 0; k < K; ++k) {
+        const bool hit = live && event_hit(a.ev[k], xr);
+        const unsigned long long votes = __ballot(hit);
+        if ((i & 63) == 0) wave_hits[i >> 6][k] = __popcll(votes);
+        if (hit && a.first_hit && a.first_hit[p * K + k] < 0) a.first_hit[p * K + k] = a.t;
+    }
+    __syncthreads();
+    if (i < K) {
+        int s = 0;
+        for (int w = 0; w < PT_BLOCK / 64; ++w) s += wave_hits[w][i];
+        a.part[(long)blockIdx.x * K + i] = s;
+    }
+}
+
+// thread k: the blocks' counts of event k in block order
+__global__ __launch_bounds__(64) void k_particle_events_finish(ParticleEventArgs a) {
+    const int k = threadIdx.x;
+    if (k >= a.K) return;
+    long long s = 0;
+    for (int b = 0; b < a.nblk; ++b) s += a.part[(long)b * a.K + k];
+    a.counts[k] = s;
+}
+
 }  // namespace pilco
 
 using namespace pilco;
@@ -240,10 +285,11 @@ static void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector
     }
 }
 
-extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
-                                       const double* x0, int P, int H, const double* eps, unsigned long long seed,
-                                       int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
-                                       double* eps_out) {
+// pilco_rollout_particles and pilco_rollout_particles_events: with n_events == 0 exactly the launches of the former
+static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                             const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
+                             double* mean, double* cov, double* reward_steps, double* particles, double* eps_out,
+                             const pilco_event* events, int n_events, long long* counts, int* first_hit) {
     if (int r = check_slot(ctx, PILCO_SLOT_DYNAMICS)) return r;
     Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
     if (ctx->nranks != 1 || ctx->comm || s.shW > 1) return fail(ctx, PILCO_E_STATE, "rollout_particles: single rank only");
@@ -261,6 +307,8 @@ extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* polic
             return fail(ctx, PILCO_E_SHAPE, "reward: unknown kind");
         if (!rewards[i].W) return fail(ctx, PILCO_E_SHAPE, "reward: W is required");
     }
+    if (const char* why = event_table_refusal(events, n_events, counts, E))
+        return fail(ctx, PILCO_E_SHAPE, std::string("rollout_particles: ") + why);
     HIPCHK(hipSetDevice(ctx->device));
     if (!s.factor_valid)
         if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
@@ -286,6 +334,14 @@ extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* polic
     ENSURE(pw.pt_part, (size_t)nblk * Q);
     ENSURE(pw.pt_stats, hstats.size());
     ENSURE(pw.pt_par, hp.size());
+    // the events' integers live in buffers of doubles: first hits [P][K] int, the blocks' counts [nblk][K] int, counts [H+1][K] long long
+    const int K = n_events;
+    const size_t fh_bytes = sizeof(int) * (size_t)P * K;
+    if (K > 0) {
+        if (first_hit) ENSURE(pw.pt_ev_first, (fh_bytes + 7) / 8);
+        ENSURE(pw.pt_ev_part, (sizeof(int) * (size_t)nblk * K + 7) / 8);
+        ENSURE(pw.pt_ev_counts, (size_t)(H + 1) * K);
+    }
 
     ParticleHeadArgs ha{};
     ParticleTailArgs ta{};
@@ -326,7 +382,24 @@ extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* polic
         hipLaunchKernelGGL(k_particle_partials, dim3(nblk), dim3(PT_BLOCK), 0, st, sa);
         hipLaunchKernelGGL(k_particle_finish, dim3((Q + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sa);
     };
+    ParticleEventArgs ea{};
+    if (K > 0) {
+        ea.P = P; ea.E = E; ea.K = K; ea.nblk = nblk;
+        ea.first_hit = first_hit ? reinterpret_cast<int*>(pw.pt_ev_first.p) : nullptr;
+        ea.part = reinterpret_cast<int*>(pw.pt_ev_part.p);
+        for (int k = 0; k < K; ++k) ea.ev[k] = events[k];
+        if (first_hit) HIPCHK(hipMemsetAsync(pw.pt_ev_first.p, 0xFF, fh_bytes, st));   // every entry -1
+    }
+    auto count_events = [&](int t) {   // the hits of the states after t steps
+        if (K == 0) return;
+        ea.x = slab(t);
+        ea.t = t;
+        ea.counts = reinterpret_cast<long long*>(pw.pt_ev_counts.p) + (size_t)t * K;
+        hipLaunchKernelGGL(k_particle_events, dim3(nblk), dim3(PT_BLOCK), 0, st, ea);
+        hipLaunchKernelGGL(k_particle_events_finish, dim3(1), dim3(64), 0, st, ea);
+    };
     stats(0, false);
+    count_events(0);
     for (int t = 0; t < H; ++t) {
         ha.x = ta.x = slab(t);
         ta.xn = slab(t + 1);
@@ -343,12 +416,17 @@ extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* polic
             hipLaunchKernelGGL(k_particle_tail, dim3((ntc + 255) / 256), dim3(256), 0, st, ta);
         }
         stats(t + 1, true);   // (its reward word: the mean reward of the pre-step states of step t)
+        count_events(t + 1);
     }
     HIPCHK(hipGetLastError());
     // one download, one synchronisation
     HIPCHK(hipMemcpyAsync(hstats.data(), pw.pt_stats.p, sizeof(double) * hstats.size(), hipMemcpyDeviceToHost, st));
     if (particles) HIPCHK(hipMemcpyAsync(particles, pw.pt_x.p, sizeof(double) * (H + 1) * PE, hipMemcpyDeviceToHost, st));
     if (eps_out && !eps && H > 0) HIPCHK(hipMemcpyAsync(eps_out, pw.pt_eps.p, sizeof(double) * H * PE, hipMemcpyDeviceToHost, st));
+    if (K > 0) {
+        HIPCHK(hipMemcpyAsync(counts, pw.pt_ev_counts.p, sizeof(long long) * (H + 1) * K, hipMemcpyDeviceToHost, st));
+        if (first_hit) HIPCHK(hipMemcpyAsync(first_hit, pw.pt_ev_first.p, fh_bytes, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     if (eps_out && eps && H > 0) memcpy(eps_out, eps, sizeof(double) * H * PE);
     for (int t = 0; t <= H; ++t) {
@@ -358,6 +436,23 @@ extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* polic
         if (t > 0 && reward_steps) reward_steps[t - 1] = row[Q - 1];
     }
     return PILCO_OK;
+}
+
+extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                       const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                       int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
+                                       double* eps_out) {
+    return rollout_particles(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps,
+                             particles, eps_out, nullptr, 0, nullptr, nullptr);
+}
+
+extern "C" int pilco_rollout_particles_events(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards,
+                                              int n_rewards, const double* x0, int P, int H, const double* eps,
+                                              unsigned long long seed, int observation_noise, double* mean, double* cov,
+                                              double* reward_steps, double* particles, double* eps_out, const pilco_event* events,
+                                              int n_events, long long* counts, int* first_hit) {
+    return rollout_particles(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps,
+                             particles, eps_out, events, n_events, counts, first_hit);
 }
 
 extern "C" int pilco_debug_particle_actions(pilco_ctx* ctx, const pilco_policy* policy, const double* x, int P, double* u) {

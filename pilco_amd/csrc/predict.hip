@@ -150,7 +150,9 @@ using namespace pilco;
 void predict_release(Slot& s) {
     if (!s.pred) return;
     PredictWork& p = *s.pred;
-    for (DevBuf* b : {&p.raw, &p.Xt, &p.Ks, &p.out, &p.pt_x, &p.pt_eps, &p.pt_rew, &p.pt_part, &p.pt_stats, &p.pt_par}) b->release();
+    for (DevBuf* b : {&p.raw, &p.Xt, &p.Ks, &p.out, &p.pt_x, &p.pt_eps, &p.pt_rew, &p.pt_part, &p.pt_stats, &p.pt_par,
+                      &p.pt_ev_first, &p.pt_ev_part, &p.pt_ev_counts})
+        b->release();
     Slot& f = p.fitc;
     for (ChainGraph* cg : {&f.g_fact, &f.g_fitc, &f.g_fitc_nlml}) chain_graph_release(*cg);
     for (DevBuf* b : {&f.Xt, &f.Yt, &f.Zt, &f.ls, &f.var, &f.noise, &f.K, &f.Linv, &f.iK, &f.beta, &f.Tscr, &f.ksplit_ws, &f.vec,

@@ -16,11 +16,15 @@ from .smgpr import SMGPR
 class ParticleTrajectories:
     """What PILCO.sample_trajectories returns: mean (n+1, E) and cov (n+1, E, E) of the particles after every step (row 0:
     the initial particles), reward (1, 1) = reward_steps.sum() -- comparable with predict(...)[2] --, reward_steps (n,),
-    particles (n+1, P, E) or None, eps (n, P, E): the standard-normal draws used."""
+    particles (n+1, P, E) or None, eps (n, P, E): the standard-normal draws used.  With events: event_counts (n+1, K), the
+    number of particles that hit event k at state t; event_prob = event_counts / P; first_hit (P, K), the first such t of
+    every particle or -1.  None without events."""
 
-    def __init__(self, mean, cov, reward_steps, particles, eps):
+    def __init__(self, mean, cov, reward_steps, particles, eps, event_counts=None, first_hit=None):
         self.mean, self.cov, self.reward_steps, self.particles, self.eps = mean, cov, reward_steps, particles, eps
         self.reward = np.asarray(reward_steps, np.float64).sum().reshape(1, 1)
+        self.event_counts, self.first_hit = event_counts, first_hit
+        self.event_prob = None if event_counts is None else event_counts / float(first_hit.shape[0])
 
     def __repr__(self):
         return "ParticleTrajectories(steps=%d, state_dim=%d, reward=%.6g)" % (self.mean.shape[0] - 1, self.mean.shape[1], self.reward[0, 0])
@@ -193,17 +197,25 @@ class PILCO:
         return M, S, R, traj
 
     def sample_trajectories(self, m_x, s_x, n, num_particles=1000, seed=0, eps=None, x0=None, observation_noise=False,
-                            return_particles=False):
+                            return_particles=False, events=None):
         """Extension: num_particles trajectories of n steps sampled through the learned dynamics on the device
         (pilco_rollout_particles), to hold against the Gaussians predict() propagates.  Every particle acts with
         compute_action(x) and moves by a draw from the GP posterior at [x, u] (latent variance; observation_noise adds the
         likelihood variance).  x0 (P, E): the initial particles; otherwise x0 = m_x + z sqrt(s_x) with z from
         np.random.default_rng(seed) and the symmetric square root of s_x (eigenvalues clipped at zero: s_x = 0 works).
         eps (n, P, E): the standard-normal draws of the steps; otherwise generated on the device from ``seed``.  An SMGPR
-        runs on the shared inducing inputs of the rollout.  Returns a ParticleTrajectories."""
-        if self._host_reward_terms():
+        runs on the shared inducing inputs of the rollout.  events: a list of K events counted on the device
+        (pilco_rollout_particles_events) -- objects with event_spec() (pilco_amd.safe's constraints) or dicts
+        dict(clauses=[(dim, low, high), ...], complement=bool) -- which fill event_counts, event_prob and first_hit of the
+        result.  A host reward term that offers event_spec() adds c * counts[t] / P to reward_steps[t], the mean over the
+        particles of c * 1[hit]: the term at zero covariance.  Such terms are counted with the caller's events, at most 8
+        together.  Any other host reward term raises NotImplementedError.  Returns a ParticleTrajectories."""
+        host = self._host_reward_terms()
+        if any(not hasattr(r, "event_spec") for _, r in host):
             raise NotImplementedError("sample_trajectories: reward terms evaluated on the host are not supported on particles; "
                                       "ask for return_particles=True and evaluate them on the returned particles")
+        K = 0 if events is None else len(events)
+        table = (list(events) if events is not None else []) + [r for _, r in host]
         E = self.state_dim
         if x0 is None:
             m = np.asarray(m_x, np.float64).reshape(1, E)
@@ -213,10 +225,18 @@ class PILCO:
         x0 = np.asarray(x0, np.float64).reshape(-1, E)
         self.mgpr._user_factors = None
         self.mgpr._ensure_factorized()
-        mean, cov, rew, parts, used = self.ctx.rollout_particles(self._policy_spec(), self._reward_terms(), x0, int(n), eps=eps,
-                                                                 seed=seed, observation_noise=observation_noise,
-                                                                 want_particles=return_particles)
-        return ParticleTrajectories(mean, cov, rew, parts, used)
+        out = self.ctx.rollout_particles(self._policy_spec(), self._reward_terms(), x0, int(n), eps=eps, seed=seed,
+                                         observation_noise=observation_noise, want_particles=return_particles,
+                                         events=table if (events is not None or host) else None)
+        mean, cov, rew, parts, used = out[:5]
+        if host:   # the mean over the particles of c * 1[hit] at the pre-step states
+            counts, P = out[5], x0.shape[0]
+            for j, (c, _) in enumerate(host):
+                for t in range(int(n)):
+                    rew[t] += c * float(counts[t, K + j]) / P
+        if events is None:
+            return ParticleTrajectories(mean, cov, rew, parts, used)
+        return ParticleTrajectories(mean, cov, rew, parts, used, np.ascontiguousarray(out[5][:, :K]), np.ascontiguousarray(out[6][:, :K]))
 
     # pilco.py:138-153
     def propagate(self, m_x, s_x):

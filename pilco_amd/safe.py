@@ -43,6 +43,12 @@ class RiskOfCollision:
         risk = (d1.cdf(self.high[0]) - d1.cdf(self.low[0])) * (d2.cdf(self.high[1]) - d2.cdf(self.low[1]))
         return risk, 0.0001 * np.ones(1)
 
+    def event_spec(self):
+        """The event on a state this risk is the probability of (PILCO.sample_trajectories counts it on particles): dims 0
+        and 2 inside their closed intervals."""
+        return dict(clauses=[(0, float(self.low[0]), float(self.high[0])), (2, float(self.low[1]), float(self.high[1]))],
+                    complement=False)
+
     def compute_reward_grad(self, m, s):
         """(risk, d risk / d m (E), d risk / d s (E, E)) of compute_reward (the reference differentiates it by TF autodiff)."""
         E = m.shape[1]
@@ -76,6 +82,12 @@ class SingleConstraint:
             risk = 1 - risk
         return risk, 0.0001 * np.ones(1)
 
+    def event_spec(self):
+        """The event on a state this risk is the probability of: one clause on ``dim`` (a missing bound: None = infinite),
+        complemented when ``inside`` is false."""
+        return dict(clauses=[(int(self.dim), None if self.low is None else float(self.low),
+                              None if self.high is None else float(self.high))], complement=not self.inside)
+
     def compute_reward_grad(self, m, s):
         """(risk, d risk / d m (E), d risk / d s (E, E)) of compute_reward."""
         E = m.shape[1]
@@ -107,6 +119,21 @@ class ObjectiveFunction:
         return list(base) + [(-self.mu, self.risk_f)]
 
 
+class RiskSample:
+    """What SafePILCO.sample_risk returns.  Over the pre-step states t = 0..n-1: risk_particles (n,), the fraction of
+    particles that hit reward_mult's event, and risk_moment_matched (n,), reward_mult.compute_reward along
+    predict_trajectory -- what the optimiser sees.  any_hit_particles: the fraction of particles that hit at some t < n;
+    any_hit_moment_matched = 1 - prod(1 - risk_moment_matched).  objective_particles = the particles' mean total reward +
+    mu * any_hit_particles; objective_moment_matched = predict(...)[2].  trajectories: the ParticleTrajectories behind them."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return "RiskSample(steps=%d, any_hit_particles=%.6g, any_hit_moment_matched=%.6g)" % (
+            self.risk_particles.shape[0], self.any_hit_particles, self.any_hit_moment_matched)
+
+
 class SafePILCO(PILCO):
     def __init__(self, data, num_induced_points=None, horizon=30, controller=None, reward_add=None,
                  reward_mult=None, m_init=None, S_init=None, name=None, mu=5.0, ctx=None):
@@ -127,6 +154,25 @@ class SafePILCO(PILCO):
 
     def _mu(self):
         return float(self.mu.numpy()) if isinstance(self.mu, Parameter) else float(self.mu)
+
+    def sample_risk(self, m_x, s_x, n, num_particles=1000, seed=0, **kwargs):
+        """Extension: the risk predict() scores a policy with, beside the learned model's own answer on particles
+        (sample_trajectories with reward_mult's event; docs/particles.md).  kwargs go to sample_trajectories (eps, x0,
+        observation_noise, return_particles).  Returns a RiskSample.  risk_moment_matched follows the reference (the variance
+        entry as the Normal scale, the steps independent in any_hit_moment_matched): it need not agree with the particles."""
+        if not hasattr(self.reward_mult, "event_spec"):
+            raise TypeError("sample_risk: reward_mult offers no event_spec()")
+        n, E = int(n), self.state_dim
+        res = self.sample_trajectories(m_x, s_x, n, num_particles=num_particles, seed=seed, events=[self.reward_mult], **kwargs)
+        traj = self.predict_trajectory(m_x, s_x, n)[3]
+        risk_mm = np.array([float(np.ravel(self.reward_mult.compute_reward(traj[t, :E].reshape(1, E), traj[t, E:].reshape(E, E))[0])[0])
+                            for t in range(n)], np.float64).reshape(n)
+        first = res.first_hit[:, 0]
+        any_p = np.count_nonzero((first >= 0) & (first < n)) / first.shape[0]
+        return RiskSample(risk_particles=res.event_prob[:n, 0].copy(), risk_moment_matched=risk_mm, any_hit_particles=any_p,
+                          any_hit_moment_matched=1.0 - float(np.prod(1.0 - risk_mm)),
+                          objective_particles=float(res.reward_steps.sum()) + self._mu() * any_p,
+                          objective_moment_matched=float(np.ravel(self.predict(m_x, s_x, n)[2])[0]), trajectories=res)
 
     def trajectory_objective(self, traj):
         """The part of predict()'s total reward that is not the additive reward, mu (1 - prod_t (1 - risk_t)), and its
