@@ -109,6 +109,13 @@ int pilco_gp_predict(pilco_ctx* ctx, int slot, const double* m, const double* s,
  * bounded memory for any Nt. */
 int pilco_gp_predict_points(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int output, const double* Z_all,
                             double* mean, double* var);
+/* The same posterior with its derivatives with respect to the test input (extension; docs/predict_jacobians.md):
+ *   dmean (E, Nt, D) = d mean_e(x_t) / d x_d,   dvar (E, Nt, D) = d var_e(x_t) / d x_d      (output-major, like mean and var).
+ * mean and var may each be NULL; where given they hold the bits pilco_gp_predict_points returns.  Arguments, refusals and
+ * chunking as for pilco_gp_predict_points; dmean and dvar must not be NULL.  A test point's derivatives are summed in a
+ * fixed order that depends on its own coordinates only: the same bits alone, in any batch and for one output or all. */
+int pilco_gp_predict_points_jac(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int output, const double* Z_all,
+                                double* mean, double* var, double* dmean, double* dvar);
 
 /* ------------------------------------------------------------------ rollout */
 typedef enum pilco_policy_kind {

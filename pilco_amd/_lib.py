@@ -94,6 +94,7 @@ SIGNATURES = {
     "pilco_gp_set_factors": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "pilco_gp_predict": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "pilco_gp_predict_points": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "pilco_gp_predict_points_jac": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                 _dp, _dp, _dp, _dp]),
     "pilco_rollout_particles": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
@@ -372,6 +373,24 @@ class Context:
         var = np.empty((rows, Nt))
         self._chk(self.lib.pilco_gp_predict_points(self.h, slot, _ptr(Xs), Nt, int(output), _ptr(Za), _ptr(mean), _ptr(var)))
         return mean, var
+
+    def gp_predict_points_jac(self, slot, Xs, D, E, output=-1, Z_all=None):
+        """gp_predict_points with the derivatives with respect to the test input: (mean, var, dmean, dvar), mean and var
+        (E, Nt) with the bits of gp_predict_points, dmean and dvar (E, Nt, D); one row for 0 <= output < E."""
+        Xs = _f64(Xs)
+        if Xs.ndim != 2 or Xs.shape[1] != D:
+            raise ValueError(f"test inputs must be (Nt, {D})")
+        Nt = Xs.shape[0]
+        Za = None
+        if Z_all is not None:
+            Za = _f64(Z_all)
+            Za = _f64(Za, (E, Za.shape[-2], D))
+        rows = E if output < 0 else 1
+        mean, var = np.empty((rows, Nt)), np.empty((rows, Nt))
+        dmean, dvar = np.empty((rows, Nt, D)), np.empty((rows, Nt, D))
+        self._chk(self.lib.pilco_gp_predict_points_jac(self.h, slot, _ptr(Xs), Nt, int(output), _ptr(Za), _ptr(mean), _ptr(var),
+                                                       _ptr(dmean), _ptr(dvar)))
+        return mean, var, dmean, dvar
 
     # ---- policy / reward marshalling
     def _policy(self, spec):

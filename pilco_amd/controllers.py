@@ -46,6 +46,15 @@ class LinearController:
     def compute_action(self, m, s, squash=True):
         return self.ctx.policy_action(self.policy_spec(squash), m, s)
 
+    def action_jacobian(self, x):
+        """d u / d x (U, E) of the deterministic action u = compute_action(x, 0)[0] = max_action * sin(x W^T + b) at the
+        state x (E,) (extension; host NumPy, docs/particles.md states the action)."""
+        x = np.asarray(x, np.float64).reshape(-1)
+        W = np.asarray(self.W.numpy(), np.float64)
+        a = W @ x + np.asarray(self.b.numpy(), np.float64).reshape(-1)
+        scale = np.broadcast_to(np.asarray(self.max_action, np.float64).reshape(-1), a.shape)
+        return (scale * np.cos(a))[:, None] * W
+
     def randomize(self):
         mean, sigma = 0, 1
         self.W.assign(mean + sigma * np.random.normal(size=self.W.shape))
@@ -174,6 +183,25 @@ class RbfController:
 
     def compute_action(self, m, s, squash=True):
         return self.ctx.policy_action(self.policy_spec(squash), m, s)
+
+    def action_jacobian(self, x):
+        """d u / d x (U, E) of the deterministic action u = compute_action(x, 0)[0] at the state x (E,) (extension; host
+        NumPy): u_k = max_action_k exp(-5e-7) sin(a_k), a_k = sum_i beta_ki k_k(x, c_i) with unit signal variance and
+        beta_k = (K_k + noise_k I)^-1 y_k (docs/particles.md; exp(-5e-7) is the 1e-6 variance the reference leaves at s = 0)."""
+        x = np.asarray(x, np.float64).reshape(-1)
+        C, Y = np.asarray(self._gp._X, np.float64), np.asarray(self._gp._Y, np.float64)
+        ls, noise = np.asarray(self._gp.lengthscales, np.float64), np.asarray(self._gp.noise, np.float64).reshape(-1)
+        U = Y.shape[1]
+        scale = np.broadcast_to(np.asarray(self.max_action, np.float64).reshape(-1), (U,)) * np.exp(-5e-7)
+        J = np.empty((U, x.size))
+        for k in range(U):
+            d = (C[:, None, :] - C[None, :, :]) / ls[k]
+            K = np.exp(-0.5 * np.sum(d * d, axis=-1)) + noise[k] * np.eye(C.shape[0])
+            beta = np.linalg.solve(K, Y[:, k])
+            diff = (C - x) / ls[k] ** 2                                   # (bf, E): d k_i / d x = k_i (c_i - x) / l^2
+            g = beta * np.exp(-0.5 * np.sum(((C - x) / ls[k]) ** 2, axis=-1))
+            J[k] = scale[k] * np.cos(g.sum()) * (g @ diff)
+        return J
 
     def randomize(self):
         """controllers.py:123-129, with its draw order from NumPy's global generator: model by model the centres (the

@@ -9,7 +9,7 @@ constexpr size_t PP_KS_BUDGET = size_t(1) << 24;   // doubles of cross-covarianc
 // data, targets and hyper-parameters are views of the parent slot's); pt_*: the particle rollout's buffers (particles.hip),
 // pt_ev_*: its events' integers (first hits, block counts, counts) in buffers of doubles
 struct PredictWork {
-    DevBuf raw, Xt, Ks, out;
+    DevBuf raw, Xt, Ks, out, jac, jacW;
     Slot fitc;
     DevBuf pt_x, pt_eps, pt_rew, pt_part, pt_stats, pt_par;
     DevBuf pt_ev_first, pt_ev_part, pt_ev_counts;
@@ -31,3 +31,11 @@ inline int predict_chunk_cap(int Eu, int npad) { return std::max(64, (int)(PP_KS
 // on ctx->st; does not wait for the stream.
 int predict_points_device(pilco_ctx* ctx, const PredictModel& m, const double* Xt, int ntc, int ldt, double* Ks, double* out_mean,
                           double* out_var);
+// The same chunk's input Jacobians, after predict_points_device has left its cross-covariances in Ks (predict_jac.hip):
+// dmean, dvar [Eu][ldt][D] = d mean / d x, d var / d x of the ntc test points; W is scratch of predict_jac_nops(m) * Eu * ldt *
+// npad doubles (the products L^{-1} K*, iAt K*).  Two launches on ctx->st; does not wait.
+inline int predict_jac_nops(const PredictModel& m) { return m.iAt ? 2 : 1; }
+int predict_points_jac_device(pilco_ctx* ctx, const PredictModel& m, const double* Xt, int ntc, int ldt, const double* Ks,
+                              double* W, double* dmean, double* dvar);
+// FITC operands of outputs e0 .. e0 + Eu - 1 on their own inducing inputs Z_all (host (E, M, D)), in pw.fitc
+int factorize_own_z(pilco_ctx* ctx, Slot& s, PredictWork& pw, const double* Z_all, int e0, int Eu);

@@ -150,7 +150,7 @@ using namespace pilco;
 void predict_release(Slot& s) {
     if (!s.pred) return;
     PredictWork& p = *s.pred;
-    for (DevBuf* b : {&p.raw, &p.Xt, &p.Ks, &p.out, &p.pt_x, &p.pt_eps, &p.pt_rew, &p.pt_part, &p.pt_stats, &p.pt_par,
+    for (DevBuf* b : {&p.raw, &p.Xt, &p.Ks, &p.out, &p.jac, &p.jacW, &p.pt_x, &p.pt_eps, &p.pt_rew, &p.pt_part, &p.pt_stats, &p.pt_par,
                       &p.pt_ev_first, &p.pt_ev_part, &p.pt_ev_counts})
         b->release();
     Slot& f = p.fitc;
@@ -171,7 +171,7 @@ static void view(DevBuf& b, double* p) {
 
 // FITC operands (Luu^{-1}, iAt, beta) of outputs e0 .. e0 + Eu - 1, each on its own inducing inputs Z_all[e] (host (E, M, D)):
 // pilco_factorize_fitc on the prediction slot, whose Zt holds one point set per output
-static int factorize_own_z(pilco_ctx* ctx, Slot& s, PredictWork& pw, const double* Z_all, int e0, int Eu) {
+int factorize_own_z(pilco_ctx* ctx, Slot& s, PredictWork& pw, const double* Z_all, int e0, int Eu) {
     Slot& f = pw.fitc;
     const int D = s.D, M = s.M, Mp = s.npad;
     f.N = s.N; f.D = D; f.E = Eu; f.M = M; f.Npad = s.Npad; f.npad = Mp; f.n = M;

@@ -138,6 +138,22 @@ class MGPR:
             raise NotImplementedError("predict_f: only full_cov=False (the marginal variances) is supported")
         return self._predict_points(Xnew)
 
+    def _predict_points_jac(self, Xnew, output=-1):
+        """(mean, var, dmean, dvar) at Xnew (Nt, D): (Nt, E), (Nt, E) and (Nt, E, D) twice; E = 1 for one output."""
+        self._user_factors = None
+        self._ensure_factorized()
+        mean, var, dmean, dvar = self.ctx.gp_predict_points_jac(
+            self._slot, np.asarray(Xnew, np.float64).reshape(-1, self.num_dims), self.num_dims, self.num_outputs, output,
+            self._own_inducing())
+        return (tensor_value(mean.T), tensor_value(var.T), tensor_value(dmean.transpose(1, 0, 2)),
+                tensor_value(dvar.transpose(1, 0, 2)))
+
+    def predict_f_jacobian(self, Xnew):
+        """predict_f with the derivatives of mean and latent variance with respect to the input (extension;
+        pilco_gp_predict_points_jac, docs/predict_jacobians.md): (mean, var, dmean, dvar), mean and var (Nt, E) with the
+        bits of predict_f, dmean[t, e, d] = d mean_e(x_t) / d x_d and dvar likewise, (Nt, E, D)."""
+        return self._predict_points_jac(Xnew)
+
     def predict_y(self, Xnew):
         """predict_f with every output's likelihood variance added to its variance (extension)."""
         mean, var = self._predict_points(Xnew)

@@ -30,6 +30,22 @@ class ParticleTrajectories:
         return "ParticleTrajectories(steps=%d, state_dim=%d, reward=%.6g)" % (self.mean.shape[0] - 1, self.mean.shape[1], self.reward[0, 0])
 
 
+class Linearization:
+    """What PILCO.linearize returns: the local model x' ~ x_next + A (x - x0) + B (u - u0) of the learned dynamics at
+    (x0, u0).  x_next (Nt, E) = x + posterior mean, var (Nt, E) its latent variance, A (Nt, E, E) = I + d mean / d x,
+    B (Nt, E, U) = d mean / d u, dvar_dx (Nt, E, E), dvar_du (Nt, E, U), u (Nt, U); K (Nt, U, E), the controller's
+    action Jacobian, and A_cl = A + B K where the action was the controller's own, else None.  A single state: the same
+    fields without the leading axis."""
+    fields = ("x_next", "var", "A", "B", "dvar_dx", "dvar_du", "u", "K", "A_cl")
+
+    def __init__(self, **kw):
+        for f in self.fields:
+            setattr(self, f, kw[f])
+
+    def __repr__(self):
+        return "Linearization(A%s, B%s%s)" % (np.shape(self.A), np.shape(self.B), "" if self.K is None else ", closed loop")
+
+
 class PILCO:
     def __init__(self, data, num_induced_points=None, horizon=30, controller=None,
                  reward=None, m_init=None, S_init=None, name=None, ctx=None):
@@ -177,6 +193,43 @@ class PILCO:
 
     def compute_action(self, x_m):
         return self.controller.compute_action(x_m, np.zeros([self.state_dim, self.state_dim]))[0]
+
+    def linearize(self, x, u=None):
+        """Extension: the learned dynamics linearised at the state(s) x (E,) or (Nt, E) and the action(s) u (U,) or (Nt, U)
+        -- by default the controller's compute_action(x); a model without control inputs takes no u.  One device call for
+        the model (MGPR.predict_f_jacobian at [x, u]); the default action and K cost one compute_action call and one host
+        action_jacobian (for an RbfController a solve for beta) per state.  Returns a Linearization.  ValueError for a u
+        given to a model without control, a u of another shape than (Nt, control_dim), or no u and no controller."""
+        E, Ud = self.state_dim, self.control_dim
+        x = np.asarray(x, np.float64)
+        single = x.ndim == 1
+        if x.ndim > 2 or x.shape[-1] != E:
+            raise ValueError(f"linearize: x must be ({E},) or (Nt, {E})")
+        X = x.reshape(-1, E)
+        Nt = X.shape[0]
+        K = None
+        if Ud == 0:
+            if u is not None:
+                raise ValueError("linearize: the model has no control input, u must be None")
+            U = np.empty((Nt, 0))
+        elif u is None:
+            if self.controller is None:
+                raise ValueError("linearize: no controller, give u")
+            U = np.stack([np.asarray(self.compute_action(X[t:t + 1]), np.float64).reshape(-1) for t in range(Nt)])
+            K = np.stack([self.controller.action_jacobian(X[t]) for t in range(Nt)])
+        else:
+            U = np.asarray(u, np.float64)
+            if U.shape != ((Ud,) if single else (Nt, Ud)):
+                raise ValueError(f"linearize: u must be {(Ud,) if single else (Nt, Ud)}, got {U.shape}")
+            U = U.reshape(Nt, Ud)
+        mean, var, dmean, dvar = (np.asarray(a) for a in self.mgpr.predict_f_jacobian(np.hstack([X, U])))
+        A = np.eye(E)[None] + dmean[..., :E]          # the GP predicts differences (pilco.py:138-153)
+        B = dmean[..., E:]
+        out = dict(x_next=X + mean, var=var, A=A, B=B, dvar_dx=dvar[..., :E], dvar_du=dvar[..., E:], u=U, K=K,
+                   A_cl=None if K is None else A + B @ K)
+        if single:
+            out = {k: (None if v is None else v[0]) for k, v in out.items()}
+        return Linearization(**out)
 
     # pilco.py:118-136
     def predict(self, m_x, s_x, n):

@@ -124,6 +124,11 @@ class GPModelView:
             raise NotImplementedError("predict_f: only full_cov=False, full_output_cov=False (the marginal variances) is supported")
         return self._owner._predict_points(Xnew, self.index)
 
+    def predict_f_jacobian(self, Xnew):
+        """predict_f of this output with the derivatives with respect to the input (extension): (mean, var, dmean, dvar),
+        (Nt, 1), (Nt, 1), (Nt, 1, D), (Nt, 1, D)."""
+        return self._owner._predict_points_jac(Xnew, self.index)
+
     def predict_y(self, Xnew, full_cov=False, full_output_cov=False):
         """gpflow's Gaussian-likelihood predict_y: predict_f with the likelihood variance added to the variance."""
         mean, var = self.predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
