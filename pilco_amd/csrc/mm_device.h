@@ -315,6 +315,14 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
     return r;
 }
 
+// 1 / sqrt(det) of a determinant formed as a running product of pivots.  The product of finite pivots can overflow (D = 32 with
+// s_dd / l_d^2 ~ 4e9 in every dimension): the estimate of +inf is 0 and the Newton step's -0.5 * inf * 0 is NaN, where the
+// formula's value is 0.  Every finite determinant keeps fast_rsqrt's bits.
+__device__ __forceinline__ double det_rsqrt(double det) {
+    const double r = fast_rsqrt(det);
+    return det > 1.7976931348623157e308 ? 0.0 : r;
+}
+
 // Unpivoted Gauss-Jordan with the matrix in registers: lane c of ONE wave holds column c of the
 // DT x 2DT augmented matrix [A | B].  Per pivot the multipliers (column k) are broadcast from lane k
 // with v_readlane; no LDS, no barriers (an LDS-broadcast variant measured slower at DT = 12).  On return

@@ -107,7 +107,7 @@ __device__ __forceinline__ void prep_mean_block(const MMModel& md, const MMWork&
             for (int r = 0; r < DT; ++r)
                 if (r < D) s_T[r * DT + cc] = col[r] * s_ia[r] * s_ia[cc];
         }
-        if (lane == 0) s_sc[1] = var_a * fast_rsqrt(detB);
+        if (lane == 0) s_sc[1] = var_a * det_rsqrt(detB);
     } else if (act) {
         // the other seven waves stage the centred points of the chunk's first 512 rows meanwhile
         // (all of a thread's requests first, then the stores: element after element the loop was twelve L2 round trips in a
@@ -549,7 +549,7 @@ __device__ __forceinline__ void prep_work(const MMModel& md, const MMWork& wk, c
                 if (r < D) s_Q[r * DT + (c - DT)] = 0.5 * col[r];
         }
         if (lane == 0) {
-            s_sc[0] = fast_rsqrt(det);
+            s_sc[0] = det_rsqrt(det);
             if (by == 0) store_wt(&wk.pair_isdet[pl], s_sc[0]);
         }
     }
