@@ -119,6 +119,17 @@ int pilco_debug_poison(pilco_ctx* ctx, int slot, int which);
  * out3 = (first wave holding a partial of pair k, slot of the pair in that wave (0/1), last such wave). */
 int pilco_debug_sk_boundary(int w, int waves, int nd, int tdiag, int toff, int ud, int uo, int n_pairs);
 int pilco_debug_sk_pair_waves(int k, int waves, int nd, int tdiag, int toff, int ud, int uo, int n_pairs, int* out3);
+/* Test aid: the stream-K cut of the dynamics slot's current workspace (after a rollout with the stream-K pair kernel) as the
+ * DEVICE computes it: a small kernel with the pair kernel's parameter list calls the device functions the pair kernel calls
+ * (the division-free forms where the host found them exact) for every wave.
+ * out: PILCO_SK_PROBE_HEAD words {waves, nd, tdiag, toff, steps T, ud, uo, local pairs, 1 if the division-free forms are in
+ * use, npad}, then PILCO_SK_PROBE_WORDS words per wave {first step, end, and of the first segment: local pair, row tile,
+ * column step, steps left in the row; slot of that pair's partial (wave - first wave of the pair); the pair's outputs a, b}
+ * (-1 from the third on for a wave without a step).  n: words out holds; PILCO_E_SHAPE if that is too few, PILCO_E_STATE
+ * without a stream-K cut. */
+#define PILCO_SK_PROBE_HEAD 10
+#define PILCO_SK_PROBE_WORDS 9
+int pilco_debug_sk_cut_probe(pilco_ctx* ctx, int* out, int n);
 /* Time `reps` factorisations (invalidating the cache each time): ms per factorisation. */
 int pilco_factorize_timed(pilco_ctx* ctx, int slot, int reps, float* ms_each);
 

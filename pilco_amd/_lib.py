@@ -138,6 +138,7 @@ SIGNATURES = {
     "pilco_debug_buffer": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_long]),
     "pilco_debug_sk_boundary": (C.c_int, [C.c_int] * 8),
     "pilco_debug_sk_pair_waves": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
+    "pilco_debug_sk_cut_probe": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
     "pilco_comm_unique_id": (C.c_int, [_vp]),
     "pilco_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int]),
     "pilco_shard_set": (C.c_int, [_vp, C.c_int, C.c_int]),
@@ -766,6 +767,20 @@ class Context:
         buf = (C.c_int * len(self.GEOMETRY_FIELDS))()
         self._chk(self.lib.pilco_debug_geometry(self.h, buf, len(buf)))
         return {name: int(buf[i]) for i, name in enumerate(self.GEOMETRY_FIELDS)}
+
+    SK_PROBE_HEAD = ("waves", "nd", "tdiag", "toff", "total", "ud", "uo", "PL", "fast", "npad")
+    SK_PROBE_WORDS = ("begin", "end", "pl", "ti", "sidx", "cnt", "slot", "a", "b")
+
+    def sk_cut_probe(self):
+        """The stream-K cut of the dynamics slot's current workspace as the device computes it (include/pilco_hip_dev.h:
+        pilco_debug_sk_cut_probe): (head dict keyed by SK_PROBE_HEAD, int array (waves, len(SK_PROBE_WORDS)))."""
+        g = self.geometry()
+        n = len(self.SK_PROBE_HEAD) + max(g["sk_waves"], 0) * len(self.SK_PROBE_WORDS)
+        buf = (C.c_int * n)()
+        self._chk(self.lib.pilco_debug_sk_cut_probe(self.h, buf, n))
+        a = np.ctypeslib.as_array(buf).copy()
+        head = {name: int(a[i]) for i, name in enumerate(self.SK_PROBE_HEAD)}
+        return head, a[len(self.SK_PROBE_HEAD):].reshape(head["waves"], len(self.SK_PROBE_WORDS))
 
     def debug_blocks(self, n):
         buf = (C.c_ulonglong * n)()

@@ -58,6 +58,7 @@ int build_work(pilco_ctx* ctx, Slot& s) {
     wk.sk_waves = 0;
     wk.sk_maxw = 0;
     wk.sk_pls = 0;
+    wk.skm = SkMagic{};
     if (ctx->variant == 0 && wk.PL > 0) {
         int tdiag, toff;
         mm_pair_sk_steps(npad, &tdiag, &toff);
@@ -91,6 +92,7 @@ int build_work(pilco_ctx* ctx, Slot& s) {
         wk.sk_toff = toff;
         wk.sk_ud = ud;
         wk.sk_uo = uo;
+        wk.skm = mm_sk_magic(wk, npad);
         wk.sk_maxw = mm_sk_maxw(wk);
         wk.sk_pls = round_up(wk.PL, 16);
     }

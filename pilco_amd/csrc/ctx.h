@@ -282,6 +282,8 @@ struct RolloutPlan {
     double* jrec = nullptr;              // Jacobian tape (bwd.hip): the dynamics step runs launch_mm_jac and writes jrec[t]
     size_t jstride = 0;
     StepRoute route;
+    double* host_out = nullptr;          // pilco_rollout / batch lanes: pinned [E | E*E | 1] result block the closing launch of a fused-head
+                                         // rollout fills (k_glue's second parameter, launch_glue); nullptr: the caller downloads state and reward itself
 };
 int rollout_run(pilco_ctx* ctx, RolloutPlan& plan, int H, const double* m0, const double* S0);   // run_rollout with (m0, S0) uploaded from the caller's memory
 // grad_route.hip

@@ -35,9 +35,9 @@ void launch_const_rows(hipStream_t st, double* a_row, int nA, double* b_row, int
     hipLaunchKernelGGL(k_const_rows, dim3((npad + 255) / 256, nb), dim3(256), 0, st, a_row, nA, b_row, nB, bs, npad, n);
 }
 
-__global__ __launch_bounds__(256) void k_glue(GlueArgs g) {
+__global__ __launch_bounds__(256) void k_glue(GlueArgs g, double* host_out) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
-    kernarg_warm<(int)sizeof(GlueArgs) + 64>();
+    kernarg_warm<(int)sizeof(GlueArgs) + 8 + 64>();
     const int E = g.E, t = threadIdx.x;
     GlueLds L;
     glue_lds_carve(g, sm, L);
@@ -63,6 +63,12 @@ __global__ __launch_bounds__(256) void k_glue(GlueArgs g) {
         return;
     }
     glue_body(g, L, true);
+    if (host_out) {   // the rollout's closing launch: state H (the link's LDS copy) and the finished reward, straight to the host
+        __syncthreads();
+        if (t < E) host_out[t] = L.mx[t];
+        for (int e = t; e < E * E; e += blockDim.x) host_out[E + e] = L.sx[e];
+        if (t == 0) host_out[E + E * E] = g.reward[0];
+    }
 }
 
 __global__ void k_stamp(unsigned long long* dbg, int slot) {
@@ -72,8 +78,8 @@ void launch_stamp(hipStream_t st, unsigned long long* dbg, int slot) {
     hipLaunchKernelGGL(k_stamp, dim3(1), dim3(64), 0, st, dbg, slot);
 }
 
-void launch_glue(hipStream_t st, const GlueArgs& g, bool with_reward_block) {
-    launch_lds<k_glue>(dim3(with_reward_block ? 2 : 1), dim3(256), sizeof(double) * glue_lds_doubles_for(g), st, g);
+void launch_glue(hipStream_t st, const GlueArgs& g, bool with_reward_block, double* host_out) {
+    launch_lds<k_glue>(dim3(with_reward_block ? 2 : 1), dim3(256), sizeof(double) * glue_lds_doubles_for(g), st, g, host_out);
 }
 
 }  // namespace pilco

@@ -28,6 +28,33 @@ struct MMModel {
     int bW, bEL;
 };
 
+// The stream-K cut of the pair kernel without a division (pair_device.h).  SkMagic: what the host adds to the geometry
+// MMWork::sk_* when the workspace is built (build_work: sk_cut_make) -- with it a wave gets its range, the decode of a segment
+// start and its partial slot from 32-bit multiplies, shifts and compares.  floor(n / d) = mulhi(n, m_d) >> shift_d for every n
+// the cut produces; C, the length of the cost line, is cq waves + cr.  One 64-byte line at the END of MMWork (no other field
+// of the workspace moves).  SkCut: geometry and constants together, as the forms take them: the host's sk_cut_make returns one,
+// the kernel assembles one from its argument segment where it needs it (sk_cut_arg) instead of holding 22 scalar registers
+// across the column loop.
+struct SkMagic {
+    unsigned fast;        // 1: the forms are exact for this shape (sk_cut_make proves the ranges); 0: the kernel keeps the division forms
+    unsigned cq, cr;      // C = cq * waves + cr, cr < waves:  floor(w C / waves) = w cq + floor(w cr / waves)
+    unsigned Ud;          // cost of the diagonal steps: nd * tdiag * ud
+    unsigned m_waves, m_ud, m_uo, m_tdiag, m_toff, m_ns;   // multipliers of the divisors waves, ud, uo, tdiag, toff, ns = npad / 16
+    unsigned m_inv;       // floor(2^s waves / C): the wave of a cost (sk_wave_of_fast), one step of fix-up away
+    unsigned sh0;         // shifts, a byte each: waves | ud << 8 | uo << 16 | tdiag << 24
+    unsigned sh1;         // toff | ns << 8 | s << 16
+    unsigned pad_[3];
+};
+static_assert(sizeof(SkMagic) == 64, "SkMagic is one 64-byte line of the kernel arguments");
+struct SkCut {
+    unsigned fast;
+    int waves, total, nd, tdiag, toff, ud, uo;   // = MMWork::sk_waves, sk_total, sk_nd, sk_tdiag, sk_toff, sk_ud, sk_uo
+    unsigned cq, cr, Ud;
+    unsigned nd_steps;    // nd * tdiag
+    unsigned ns;          // npad / 16: column steps of a full row
+    unsigned m_waves, m_ud, m_uo, m_tdiag, m_toff, m_ns, m_inv, sh0, sh1;
+};
+
 // Per-slot workspace of one step.
 struct MMWork {
     double* in_m;        // [D]      input mean  (joint state-action mean)
@@ -73,6 +100,7 @@ struct MMWork {
                          // the CUs it would leave idle (grid y = NCH * NCS, NT = NCH * NCS partials per pair); 1 elsewhere
     const double* exp_tab;    // [n] 2^(j/n) biased (mm_exp_table_fill), n = mm_exp_table_size(), for the table-driven fp64 exp of the pair kernel
     int PL, EL, P, KP, NCH, NCHM, NT, SEG, OUTOFF, rank, nranks;  // NCH / NCHM: row chunks of the pair / mean-part prep workgroups; OUTOFF: offset of the output records inside a segment
+    SkMagic skm;         // the stream-K cut's division-free constants (variant 0; zeros elsewhere).  Last: k_mm_pair_sk alone reads them
 };
 
 struct RewardDev {
@@ -178,10 +206,14 @@ void launch_mm_pair(hipStream_t st, const MMModel& md, const MMWork& wk, int var
 int mm_pair_sk_capacity(int KP, bool vsep, bool allow_env = true);   // allow_env: PILCO_SK_WAVES may override
 void mm_pair_sk_steps(int npad, int* tdiag, int* toff);
 int mm_sk_boundary(int w, int waves, int nd_steps, int total, int ud, int uo);
+void launch_sk_cut_probe(hipStream_t st, const MMModel& md, const MMWork& wk, int* out);   // out [sk_waves][PILCO_SK_PROBE_WORDS] on the device
+SkMagic mm_sk_magic(const MMWork& wk, int npad);   // the constants for a workspace's stream-K geometry sk_* (fast = 0 where a range does not fit)
 int mm_sk_maxw(const MMWork& wk);
 int mm_sk_max_pairs(int waves, int nd, int tdiag, int toff, int n_pairs, int ud, int uo);   // most local pairs one wave's range touches
 void mm_sk_pair_waves(int k, int waves, int nd, int tdiag, int toff, int total, int ud, int uo, int* wlo, int* fslot, int* whi);   // needs the sk_* geometry fields and PL
-void launch_glue(hipStream_t st, const GlueArgs& g, bool with_reward_block = false);
+// host_out: the closing launch of pilco_rollout / a pilco_rollout_batch lane -- a pinned host block [E | E*E | 1] that also takes the
+// final state and the finished reward (no download copies behind the rollout); nullptr elsewhere
+void launch_glue(hipStream_t st, const GlueArgs& g, bool with_reward_block = false, double* host_out = nullptr);
 size_t glue_lds_bytes(int E, int D);
 // tile-partial counts per pair for a variant (NT) and the number of row chunks of the prep kernel
 int mm_pair_nt(int npad, int variant, int PL);

@@ -70,6 +70,9 @@ int mm_sk_maxw(const MMWork& wk) {
 int mm_sk_boundary(int w, int waves, int nd_steps, int total, int ud, int uo) {
     return sk_boundary_of(w, waves, nd_steps, total, ud, uo);
 }
+SkMagic mm_sk_magic(const MMWork& wk, int npad) {
+    return sk_magic_of(sk_cut_make(wk.sk_waves, wk.sk_nd, wk.sk_tdiag, wk.sk_toff, wk.sk_total, wk.sk_ud, wk.sk_uo, npad));
+}
 int mm_sk_max_pairs(int waves, int nd, int tdiag, int toff, int n_pairs, int ud, int uo) {
     return sk_max_pairs_per_wave(waves, nd, tdiag, toff, n_pairs, ud, uo);
 }
@@ -77,6 +80,7 @@ void mm_sk_pair_waves(int k, int waves, int nd, int tdiag, int toff, int total, 
     sk_pair_waves(k, waves, nd, tdiag, toff, total, ud, uo, *wlo, *fslot, *whi);
 }
 
+// (parameter order: sk_cut_arg reads the cut from the argument segment of a kernel that starts with (MMModel, MMWork) by value)
 template <int KC, bool VSEP>
 __global__ __launch_bounds__(256, (KC <= 4 && PAIR_MINW < 3) ? 3 : PAIR_MINW) void k_mm_pair_sk(MMModel md, MMWork wk) {
     __shared__ double tab[FEXP_TN];
@@ -84,6 +88,7 @@ __global__ __launch_bounds__(256, (KC <= 4 && PAIR_MINW < 3) ? 3 : PAIR_MINW) vo
     TabArrival ta;
     ta.request(wk.exp_tab, tab);   // requested here, stored behind the first tile's operand requests
     const int lane = threadIdx.x & 63;
+    const SkArgPtr skp = sk_cut_argptr();   // (the cut is read there, where it is needed: sk_cut_arg)
     // XCD-aware placement: workgroups are dealt round-robin over the 8 XCDs (own L2 each), so workgroup b takes
     // position (b % 8) * (blocks / 8) + b / 8 of the cost line: the waves of one XCD cover one contiguous eighth of it
     // and its L2 holds the operands of ~1/8 of the pairs instead of all of them.
@@ -100,11 +105,14 @@ __global__ __launch_bounds__(256, (KC <= 4 && PAIR_MINW < 3) ? 3 : PAIR_MINW) vo
     }
 #endif
     DBG_STAMP(wk, 16, w == 0 && lane == 0);
+#ifdef PAIR_START_STAMP   // start-up of wave 0 (16 -> 46) and of the last wave (38 -> 39): kernel entry to first operand requests issued
+    DBG_STAMP(wk, 38, w == wk.sk_waves - 1 && lane == 0);
+    if (wk.dbg && lane == 0) ta.stamp = (w == 0) ? wk.dbg + 46 : (w == wk.sk_waves - 1) ? wk.dbg + 39 : nullptr;
+#endif
     if (wk.dbg && w == 0 && lane == 0) wk.dbg[32] = clock64();     // shader-clock counter beside the 100 MHz wall clock: tools/ derive the engine clock under this load
-    const int nd_steps = wk.sk_nd * wk.sk_tdiag;
     double out0, out1;
     int p0, p1;
-    sk_wave_range<KC, VSEP>(md, wk, tab, w, lane, out0, out1, p0, p1, &ta, PAIR_FAIR != 0);
+    sk_wave_range<KC, VSEP>(md, wk, skp, tab, w, lane, out0, out1, p0, p1, &ta, PAIR_FAIR != 0);
     ta.land();   // (a wave without a single step still owes the workgroup its barrier)
     for (int off = 32; off > 0; off >>= 1) {
         out0 += __shfl_down(out0, off);
@@ -114,11 +122,7 @@ __global__ __launch_bounds__(256, (KC <= 4 && PAIR_MINW < 3) ? 3 : PAIR_MINW) vo
         // slot-major layout sk_part[slot][pair], slot = wave - (first wave of the pair): the reader (the serial link)
         // gets coalesced loads with addresses from its thread index alone.  A wave that enters a pair from a previous one
         // IS that pair's first wave (slot 0); only the first touched pair needs the closed form.
-        if (p0 >= 0) {
-            const long S0 = (p0 < wk.sk_nd) ? (long)p0 * wk.sk_tdiag : (long)wk.sk_nd * wk.sk_tdiag + (long)(p0 - wk.sk_nd) * wk.sk_toff;
-            const int wlo = sk_wave_of(S0, wk.sk_waves, nd_steps, wk.sk_total, wk.sk_ud, wk.sk_uo);
-            wk.sk_part[(long)(w - wlo) * wk.sk_pls + p0] = out0;
-        }
+        if (p0 >= 0) wk.sk_part[(long)sk_first_slot(sk_cut_arg(skp), w, p0) * wk.sk_pls + p0] = out0;
         if (p1 >= 0) wk.sk_part[p1] = out1;
     }
     DBG_STAMP(wk, 17, w == 0 && lane == 0);
@@ -195,6 +199,37 @@ __global__ __launch_bounds__(256) void k_mm_pair_valu(MMModel md, MMWork wk) {
     }
 }
 #endif   // PILCO_DEV
+
+// test aid (pilco_debug_sk_cut_probe): the cut as the stream-K kernel sees it -- same parameter list, so the same place of
+// the cut in the argument segment, and the same device functions -- for every wave: begin, end, the decode of its first
+// segment (pair, row tile, column step, steps left in the row), the slot of that pair's partial and the pair's outputs
+// (parameter order: sk_cut_arg reads the cut from the argument segment of a kernel that starts with (MMModel, MMWork) by value)
+__global__ __launch_bounds__(256) void k_sk_cut_probe(MMModel md, MMWork wk, int* out) {
+    const SkArgPtr skp = sk_cut_argptr();
+    const SkCut c = sk_cut_arg(skp);
+    const int w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= c.waves) return;
+    int* o = out + (long)w * PILCO_SK_PROBE_WORDS;
+    const int step = sk_boundary(c, w), end = sk_boundary(c, w + 1);
+    o[0] = step;
+    o[1] = end;
+    for (int i = 2; i < PILCO_SK_PROBE_WORDS; ++i) o[i] = -1;
+    if (step >= end) return;
+    int pl, ti, sidx, cnt, a, b;
+    sk_decode(c, step, pl, ti, sidx, cnt);
+    if (c.fast) sk_pair_ab_fast(pl * wk.nranks + wk.rank, md.E, a, b);
+    else local_pair_ab(wk, md.E, pl, a, b);
+    o[2] = pl;
+    o[3] = ti;
+    o[4] = sidx;
+    o[5] = cnt;
+    o[6] = sk_first_slot(sk_cut_arg(skp), w, pl);
+    o[7] = a;
+    o[8] = b;
+}
+void launch_sk_cut_probe(hipStream_t st, const MMModel& md, const MMWork& wk, int* out) {
+    hipLaunchKernelGGL(k_sk_cut_probe, dim3((wk.sk_waves + 255) / 256), dim3(256), 0, st, md, wk, out);
+}
 
 static int pair_njb(int npad, int PL) {
     const int nb = npad / 64;

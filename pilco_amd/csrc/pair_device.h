@@ -63,11 +63,17 @@ struct TabArrival {
     double v[NV];    // this thread's table entries (requested, perhaps not yet arrived)
     double* lds;     // the table in LDS
     bool pending;    // not stored yet (wave-uniform)
+#ifdef PAIR_START_STAMP   // developer build (tools/pair_start.py): where this lane stamps "first operand requests issued", or nullptr
+    unsigned long long* stamp;
+#endif
     __device__ __forceinline__ void request(const double* __restrict__ g, double* l) {
 #pragma unroll
         for (int k = 0; k < NV; ++k) v[k] = (FEXP_TN % 256 == 0 || threadIdx.x + 256 * k < FEXP_TN) ? g[threadIdx.x + 256 * k] : 0.0;
         lds = l;
         pending = true;
+#ifdef PAIR_START_STAMP
+        stamp = nullptr;
+#endif
     }
     __device__ __forceinline__ void land() {
         if (pending) {
@@ -165,6 +171,9 @@ __device__ __forceinline__ double pair_wave(const PairOps& po, const double* __r
             }
         }
     }
+#ifdef PAIR_START_STAMP
+    if (ta && ta->pending && ta->stamp) *ta->stamp = wall_clock64();
+#endif
     if (ta) ta->land();   // (the requests above are in flight; see TabArrival)
     // one 16-column step on ring slot rg; the slot is refilled with the operands of column step j0 + 32
     auto step = [&](double (&rg)[KC + 2], const int j0) {
@@ -322,18 +331,228 @@ inline int sk_max_pairs_per_wave(int waves, int nd, int tdiag, int toff, int n_p
     }
     return most;
 }
-__device__ __forceinline__ int sk_boundary(const MMWork& wk, int w) {
-    return sk_boundary_of(w, wk.sk_waves, wk.sk_nd * wk.sk_tdiag, wk.sk_total, wk.sk_ud, wk.sk_uo);
+// ---- the same cut without a division (SkCut, moment.h).  Everything the cut divides by is a constant of the workspace, so
+// the host makes, per divisor d >= 2, the multiplier m = ceil(2^(32 + sh) / d) with 2^sh < d <= 2^(sh + 1): then
+// floor(n / d) = mulhi(n, m) >> sh for every n <= 2^31 (the error term n (m d - 2^(32 + sh)) stays below 2^(32 + sh)), and
+// m < 2^32.  sk_cut_make checks every range the forms below rely on and clears `fast` where one does not hold (a divisor of 1,
+// a cost line of 2^31 or more, more than 46340 waves: w cr would pass 2^31, more points than the root forms are tested for:
+// npad > 8192); the kernel then keeps the division forms.
+// tests/test_sk_cut_fast_cpu.py compares every form with the ones above over all shapes.
+#ifndef SK_SQRTF   // the square root of the two closed forms: one v_sqrt_f32 (1 ulp) on the device; both have an integer fix-up
+#ifdef __HIP_DEVICE_COMPILE__
+#define SK_SQRTF(x_) __builtin_amdgcn_sqrtf(x_)
+#else
+#define SK_SQRTF(x_) sqrtf(x_)
+#endif
+#endif
+__host__ __device__ inline unsigned sk_mulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
+__host__ __device__ inline unsigned sk_div(unsigned n, unsigned m, unsigned sh) { return sk_mulhi(n, m) >> sh; }
+inline bool sk_magic_make(unsigned d, unsigned& m, unsigned& sh) {
+    m = 0;
+    sh = 0;
+    if (d < 2 || d > (1u << 30)) return false;
+    while ((2u << sh) < d) ++sh;
+    m = (unsigned)((((unsigned long long)1 << (32 + sh)) + d - 1) / d);
+    return true;
+}
+inline SkCut sk_cut_make(int waves, int nd, int tdiag, int toff, int total, int ud, int uo, int npad) {
+    SkCut c{};
+    c.waves = waves; c.total = total; c.nd = nd; c.tdiag = tdiag; c.toff = toff; c.ud = ud; c.uo = uo;
+    const long nd_steps = (long)nd * tdiag;
+    const long Ud = nd_steps * ud;
+    const long C = Ud + ((long)total - nd_steps) * uo;
+    c.nd_steps = (unsigned)nd_steps;
+    c.ns = (unsigned)(npad / 16);
+    const SkCut slow = c;
+    if (waves < 2 || waves > 46340 || C <= 0 || C + ud + uo >= (1L << 31) || total <= 0 || npad < 32 || npad % 16) return slow;
+    // the two closed forms with a root work on integers that fp32 must hold exactly: b^2 and 2 PAIR_RT q (q < tdiag) below 2^24
+    // (npad <= 65504; tests/test_sk_cut_fast_cpu.py runs them over all arguments up to npad = 8192), 8 q + 1 of a pair index likewise
+    {
+        const double b = (double)(npad / 16) + 0.5 * PAIR_RT;
+        if (b * b > 16777216.0 || 2.0 * PAIR_RT * (double)tdiag > 16777216.0 || npad > 8192) return slow;
+    }
+    unsigned sw, sud, suo, std_, sto, sns;
+    bool ok = sk_magic_make((unsigned)waves, c.m_waves, sw);
+    ok = sk_magic_make((unsigned)ud, c.m_ud, sud) && ok;
+    ok = sk_magic_make((unsigned)uo, c.m_uo, suo) && ok;
+    ok = sk_magic_make((unsigned)tdiag, c.m_tdiag, std_) && ok;
+    ok = sk_magic_make((unsigned)toff, c.m_toff, sto) && ok;
+    ok = sk_magic_make((unsigned)(npad / 16), c.m_ns, sns) && ok;
+    if (!ok) return slow;
+    // the inverse: the wave of a cost x is ceil((x + 1) waves / C) - 1; ((x + 1) m_inv) >> s is less than one below
+    // (x + 1) waves / C as long as C < 2^s, and the product stays below 2^63
+    int s = 47;
+    while (s > 0 && (((unsigned long long)waves << s) / (unsigned long long)C) >> 32) --s;
+    if (C >= (1L << s)) return slow;
+    c.m_inv = (unsigned)(((unsigned long long)waves << s) / (unsigned long long)C);
+    c.cq = (unsigned)(C / waves);
+    c.cr = (unsigned)(C % waves);
+    c.Ud = (unsigned)Ud;
+    c.sh0 = sw | sud << 8 | suo << 16 | std_ << 24;
+    c.sh1 = sto | sns << 8 | (unsigned)s << 16;
+    c.fast = 1;
+    return c;
+}
+// floor(w C / waves), w <= waves
+__host__ __device__ inline unsigned sk_cost_of_wave(const SkCut& c, unsigned w) {
+    return w * c.cq + sk_div(w * c.cr, c.m_waves, c.sh0 & 255u);
+}
+__host__ __device__ inline int sk_boundary_fast(const SkCut& c, int w) {
+    if (w >= c.waves) return c.total;
+    const unsigned x = sk_cost_of_wave(c, (unsigned)w);
+    if (x <= c.Ud) return (int)sk_div(x + (unsigned)c.ud - 1u, c.m_ud, (c.sh0 >> 8) & 255u);
+    return (int)(c.nd_steps + sk_div(x - c.Ud + (unsigned)c.uo - 1u, c.m_uo, (c.sh0 >> 16) & 255u));
+}
+// sk_wave_of: the last wave whose first step is <= x -- an estimate from the inverse multiplier, at most one above, then down
+// along the forward form (exactly the wave the division form names: floor(w C / waves) <= cost(x) is its definition)
+__host__ __device__ inline int sk_wave_of_fast(const SkCut& c, unsigned x) {
+    const int waves = c.waves;
+    const unsigned cx = (x <= c.nd_steps) ? x * (unsigned)c.ud : c.Ud + (x - c.nd_steps) * (unsigned)c.uo;
+    unsigned w = (unsigned)(((unsigned long long)(cx + 1u) * c.m_inv) >> ((c.sh1 >> 16) & 255u)) + 1u;
+    if (w > (unsigned)waves - 1u) w = (unsigned)waves - 1u;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        if (sk_cost_of_wave(c, w) > cx) --w;   // (never below 0: the cost of wave 0 is 0)
+    return (int)w;
+}
+// first step of local pair k on the line
+__host__ __device__ inline unsigned sk_pair_start(const SkCut& c, int k) {
+    return (k < c.nd) ? (unsigned)k * (unsigned)c.tdiag : c.nd_steps + (unsigned)(k - c.nd) * (unsigned)c.toff;
+}
+// row tile of column step q of a diagonal pair: tile t starts at P(t) = t ns - PAIR_RT t (t - 1) / 2 (its row lost the columns
+// left of its diagonal block), so t = floor((b - sqrt(b^2 - 2 PAIR_RT q)) / PAIR_RT), b = ns + PAIR_RT / 2 -- all integers
+// below 2^24, exact in fp32 up to the root itself -- and one step of integer fix-up either way
+__host__ __device__ inline int sk_tile_start(int t, int ns) { return t * ns - PAIR_RT * (t * (t - 1) / 2); }
+__host__ __device__ inline int sk_row_tile(int q, int ns) {
+    const float b = (float)ns + 0.5f * (float)PAIR_RT;
+    const float disc = b * b - (float)(2 * PAIR_RT) * (float)q;
+    int t = (int)((b - SK_SQRTF(disc > 0.0f ? disc : 0.0f)) * (1.0f / (float)PAIR_RT));
+    if (t < 0) t = 0;
+    if (sk_tile_start(t, ns) > q) --t;
+    if (sk_tile_start(t + 1, ns) <= q) ++t;
+    return t;
+}
+// decode of a step of the line: local pair, row tile, column step of the row and the steps left in the row
+__host__ __device__ inline void sk_decode_fast(const SkCut& c, int step, int& pl, int& ti, int& sidx, int& cnt) {
+    const int ns = (int)c.ns, nd = c.nd, tdiag = c.tdiag, toff = c.toff;
+    if ((unsigned)step < c.nd_steps) {
+        pl = (int)sk_div((unsigned)step, c.m_tdiag, (c.sh0 >> 24) & 255u);
+        int q = step - pl * tdiag;
+        ti = sk_row_tile(q, ns);
+        q -= sk_tile_start(ti, ns);
+        sidx = ti * PAIR_RT + q;
+        cnt = ns - PAIR_RT * ti - q;
+    } else {
+        const unsigned r = (unsigned)step - c.nd_steps;
+        const unsigned k = sk_div(r, c.m_toff, c.sh1 & 255u);
+        const unsigned q = r - k * (unsigned)toff;
+        pl = nd + (int)k;
+        ti = (int)sk_div(q, c.m_ns, (c.sh1 >> 8) & 255u);
+        sidx = (int)q - ti * ns;
+        cnt = ns - sidx;
+    }
+}
+// the division form of the same decode (what sk_wave_range did inline; kept for shapes with fast == 0 and as the reference)
+__host__ __device__ inline void sk_decode_ref(const SkCut& g, int step, int& pl, int& ti, int& sidx, int& cnt) {
+    const int NS = (int)g.ns, nd = g.nd, tdiag = g.tdiag, toff = g.toff, nd_steps = (int)g.nd_steps;
+    int q;
+    if (step < nd_steps) {
+        pl = step / tdiag;
+        q = step - pl * tdiag;
+        ti = 0;
+        int c = NS;
+        while (q >= c) {
+            q -= c;
+            ++ti;
+            c -= PAIR_RT;
+        }
+        sidx = ti * PAIR_RT + q;
+        cnt = c - q;
+    } else {
+        const int r = step - nd_steps;
+        pl = nd + r / toff;
+        q = r - (pl - nd) * toff;
+        ti = q / NS;
+        sidx = q - ti * NS;
+        cnt = NS - sidx;
+    }
+}
+// outputs (a >= b) of order index kk (local_pair_ab without its loop): a (a - 1) / 2 <= kk - E < a (a + 1) / 2
+__host__ __device__ inline void sk_pair_ab_fast(int kk, int E, int& a, int& b) {
+    if (kk < E) {
+        a = b = kk;
+        return;
+    }
+    const int q = kk - E;
+    int t = (int)((1.0f + SK_SQRTF((float)(8 * q + 1))) * 0.5f);
+    if (t < 1) t = 1;
+    if (t * (t - 1) / 2 > q) --t;
+    if ((t + 1) * t / 2 <= q) ++t;
+    a = t;
+    b = q - t * (t - 1) / 2;
+}
+inline SkMagic sk_magic_of(const SkCut& c) {
+    SkMagic m{};
+    m.fast = c.fast; m.cq = c.cq; m.cr = c.cr; m.Ud = c.Ud; m.m_waves = c.m_waves; m.m_ud = c.m_ud; m.m_uo = c.m_uo;
+    m.m_tdiag = c.m_tdiag; m.m_toff = c.m_toff; m.m_ns = c.m_ns; m.m_inv = c.m_inv; m.sh0 = c.sh0; m.sh1 = c.sh1;
+    return m;
+}
+// The kernel's copy of the cut: read from the kernel-argument segment of a kernel with the parameters (MMModel, MMWork, ...)
+// -- uniform loads that hit the scalar cache: kernarg_warm has requested the lines -- every time it is asked for: at the wave's
+// start, at a segment change, at the wave's end.  None of its words is held across the column loop.
+typedef const __attribute__((address_space(4))) char* SkArgPtr;
+__device__ __forceinline__ SkArgPtr sk_cut_argptr() { return (SkArgPtr)__builtin_amdgcn_kernarg_segment_ptr(); }
+__device__ __forceinline__ SkCut sk_cut_arg(SkArgPtr ka) {
+    asm volatile("" : "+s"(ka));   // (a read of its own: not merged with an earlier one whose registers would have to live on)
+    typedef const __attribute__((address_space(4))) int* IP;
+    typedef const __attribute__((address_space(4))) unsigned* UP;
+    // LAYOUT: the kernel's first two parameters are (MMModel, MMWork) BY VALUE -- k_mm_pair_sk and k_sk_cut_probe (pair.hip) say so
+    // at their heads; the argument segment holds them in order at their natural alignment (tests/test_gpu_sk_cut.py reads the
+    // result back through the probe)
+    static_assert(std::is_standard_layout<MMModel>::value && std::is_standard_layout<MMWork>::value, "offsetof into the argument segment");
+    static_assert(std::is_trivially_copyable<MMModel>::value && std::is_trivially_copyable<MMWork>::value, "passed by value, bit for bit");
+    static_assert(alignof(MMModel) == 8 && alignof(MMWork) == 8, "the second parameter starts at round_up(sizeof(MMModel), 8)");
+    static_assert(sizeof(MMWork) - (offsetof(MMWork, skm) + sizeof(SkMagic)) < alignof(MMWork) && offsetof(MMWork, skm) % 4 == 0, "SkMagic is the last block of MMWork");
+    static_assert(sizeof(((MMWork*)nullptr)->sk_waves) == 4 && sizeof(((MMModel*)nullptr)->npad) == 4, "read as 32-bit words");
+    constexpr size_t WK = (sizeof(MMModel) + alignof(MMWork) - 1) / alignof(MMWork) * alignof(MMWork);   // the second parameter
+    SkCut c;
+    c.waves = *(IP)(ka + WK + offsetof(MMWork, sk_waves));
+    c.total = *(IP)(ka + WK + offsetof(MMWork, sk_total));
+    c.nd = *(IP)(ka + WK + offsetof(MMWork, sk_nd));
+    c.tdiag = *(IP)(ka + WK + offsetof(MMWork, sk_tdiag));
+    c.toff = *(IP)(ka + WK + offsetof(MMWork, sk_toff));
+    c.ud = *(IP)(ka + WK + offsetof(MMWork, sk_ud));
+    c.uo = *(IP)(ka + WK + offsetof(MMWork, sk_uo));
+    c.ns = (unsigned)(*(IP)(ka + offsetof(MMModel, npad))) >> 4;
+    c.nd_steps = (unsigned)(c.nd * c.tdiag);
+    const UP m = (UP)(ka + WK + offsetof(MMWork, skm));
+    c.fast = m[0]; c.cq = m[1]; c.cr = m[2]; c.Ud = m[3]; c.m_waves = m[4]; c.m_ud = m[5]; c.m_uo = m[6];
+    c.m_tdiag = m[7]; c.m_toff = m[8]; c.m_ns = m[9]; c.m_inv = m[10]; c.sh0 = m[11]; c.sh1 = m[12];
+    return c;
+}
+__host__ __device__ inline int sk_boundary(const SkCut& c, int w) {
+    if (c.fast) return sk_boundary_fast(c, w);
+    return sk_boundary_of(w, c.waves, (int)c.nd_steps, c.total, c.ud, c.uo);
+}
+__host__ __device__ inline void sk_decode(const SkCut& c, int step, int& pl, int& ti, int& sidx, int& cnt) {
+    if (c.fast) sk_decode_fast(c, step, pl, ti, sidx, cnt);
+    else sk_decode_ref(c, step, pl, ti, sidx, cnt);
+}
+// slot of a wave's FIRST touched pair p0 in the slot-major partial array: w - (first wave of the pair)
+__host__ __device__ inline int sk_first_slot(const SkCut& c, int w, int p0) {
+    if (c.fast) return w - sk_wave_of_fast(c, sk_pair_start(c, p0));
+    const long S0 = (p0 < c.nd) ? (long)p0 * c.tdiag : (long)c.nd * c.tdiag + (long)(p0 - c.nd) * c.toff;
+    return w - sk_wave_of(S0, c.waves, (int)c.nd_steps, c.total, c.ud, c.uo);
 }
 // One wave's share of the stream-K line (see k_mm_pair_sk): the 16-column steps [boundary(w), boundary(w + 1)) of the
 // cost line, touching at most two local pairs p0, p1 (-1: none) with the sums out0, out1 (before the wave reduction).
 template <int KC, bool VSEP, bool FENCE = false>
-__device__ __forceinline__ void sk_wave_range(const MMModel& md, const MMWork& wk, const double* __restrict__ tab, int w, int lane,
+__device__ __forceinline__ void sk_wave_range(const MMModel& md, const MMWork& wk, SkArgPtr skp, const double* __restrict__ tab, int w, int lane,
                                               double& out0, double& out1, int& p0, int& p1, TabArrival* ta = nullptr, bool fair = false) {
-    const int npad = md.npad, NS = npad / 16;
-    const int nd_steps = wk.sk_nd * wk.sk_tdiag;
-    int step = sk_boundary(wk, w);
-    const int end = sk_boundary(wk, w + 1);
+    const int npad = md.npad;
+    SkCut c = sk_cut_arg(skp);
+    int step = sk_boundary(c, w);
+    const int end = sk_boundary(c, w + 1);
     WaveProgress prog{0, end - step, -1};
     WaveProgress* wp = fair ? &prog : nullptr;
     out0 = 0.0;
@@ -343,28 +562,9 @@ __device__ __forceinline__ void sk_wave_range(const MMModel& md, const MMWork& w
     double cur = 0.0;
     int cur_pl = -1;
     while (step < end) {
-        int pl, q, ti, sidx, cnt;
-        const bool dg = step < nd_steps;
-        if (dg) {
-            pl = step / wk.sk_tdiag;
-            q = step - pl * wk.sk_tdiag;
-            ti = 0;
-            int c = NS;
-            while (q >= c) {
-                q -= c;
-                ++ti;
-                c -= PAIR_RT;
-            }
-            sidx = ti * PAIR_RT + q;
-            cnt = c - q;
-        } else {
-            const int r = step - nd_steps;
-            pl = wk.sk_nd + r / wk.sk_toff;
-            q = r - (pl - wk.sk_nd) * wk.sk_toff;
-            ti = q / NS;
-            sidx = q - ti * NS;
-            cnt = NS - sidx;
-        }
+        int pl, ti, sidx, cnt;
+        const bool dg = step < (int)c.nd_steps;
+        sk_decode(c, step, pl, ti, sidx, cnt);
         const int seg = (cnt < end - step) ? cnt : (end - step);
         if (pl != cur_pl) {
             if (cur_pl >= 0) {  // a range touches at most two pairs
@@ -375,7 +575,8 @@ __device__ __forceinline__ void sk_wave_range(const MMModel& md, const MMWork& w
             cur = 0.0;
         }
         int a, b;
-        local_pair_ab(wk, md.E, pl, a, b);
+        if (c.fast) sk_pair_ab_fast(pl * wk.nranks + wk.rank, md.E, a, b);
+        else local_pair_ab(wk, md.E, pl, a, b);
         const PairOps po = pair_ops(wk, md.D, npad, pl, b);
         const double* beta_a = md.beta + mm_beta_row(md, a) * npad;
         const double* beta_b = md.beta + mm_beta_row(md, b) * npad;
@@ -385,6 +586,7 @@ __device__ __forceinline__ void sk_wave_range(const MMModel& md, const MMWork& w
         else
             cur += pair_wave<KC, false, VSEP, FENCE>(po, nullptr, nullptr, nullptr, beta_a, beta_b, nullptr, tab, npad, i0, jbeg, jend, lane, 0, 0, 0, ta, wp);
         step += seg;
+        if (step < end) c = sk_cut_arg(skp);   // (the next segment's decode: read again behind the column loop)
     }
     if (cur_pl >= 0) {
         if (p0 < 0) {

@@ -232,6 +232,12 @@ static int plan_route(pilco_ctx* ctx, RolloutPlan& plan, int H, bool timed) {
     return PILCO_OK;
 }
 
+// single-rank fused heads (STEP_FUSED / STEP_SMALL): the closing launch hands the results to the host where the caller gave it a
+// pinned block (plan.host_out: pilco_rollout and the lanes of pilco_rollout_batch)
+static bool results_to_host(const RolloutPlan& plan, int H) {
+    return H > 0 && plan.host_out && (plan.route.step == STEP_FUSED || plan.route.step == STEP_SMALL);
+}
+
 // The reward of a state (pilco.py:133) rides in a spare workgroup of a head or prep launch: of the state the link holds in
 // LDS, or (m_x given: the three-kernel step) of the state at m_x
 static PrepReward reward_arg(const RolloutPlan& plan, const double* m_x = nullptr) {
@@ -322,7 +328,7 @@ static int enqueue_fused(pilco_ctx* ctx, const RolloutPlan& plan, const GlueArgs
     }
     GlueArgs gf = closing_args(plan, g, H, GF_PACK | GF_ASSEMBLE | GF_PROPAGATE | GF_TRAJ);
     gf.wk = wkb[(H - 1) & 1];
-    launch_glue(ctx->st, gf);
+    launch_glue(ctx->st, gf, false, results_to_host(plan, H) ? plan.host_out : nullptr);
     return PILCO_OK;
 }
 
@@ -558,7 +564,7 @@ static int run_rollout(pilco_ctx* ctx, RolloutPlan& plan, int H, Upload&& upload
         (unsigned long long)(uintptr_t)ctx->slot[1].var.p,
         (unsigned long long)(uintptr_t)plan.jrec, (unsigned long long)plan.jstride, (unsigned long long)(uintptr_t)s.jac_rowmom.p,
         (unsigned long long)(uintptr_t)s.jac_cpart.p, (unsigned long long)(uintptr_t)s.jac_part.p, (unsigned long long)(uintptr_t)s.jac_head.p,
-        (unsigned long long)(uintptr_t)s.jac_np.p};
+        (unsigned long long)(uintptr_t)s.jac_np.p, (unsigned long long)(uintptr_t)plan.host_out};
     // the shapes themselves: buffers only grow (DevBuf::ensure), so a smaller or differently laid-out model keeps every address
     // above -- an exact model after a sparse one with M = N keeps n and npad too, and would replay the graph that reads Zt
     const Slot& ps = ctx->slot[PILCO_SLOT_POLICY];
@@ -648,7 +654,8 @@ static int rollout_begin(pilco_ctx* ctx, const pilco_policy* policy, const pilco
     RolloutPlan& plan = rc.plan;
     if (int r = setup_rollout(ctx, policy, rewards, n_rewards, H, traj != nullptr, plan)) return r;
     const int E = plan.E;
-    // one pinned staging area: [m0 | S0] up in ONE asynchronous copy, [m_H | S_H] and the reward down in two, one host
+    // one pinned staging area: [m0 | S0] up in ONE asynchronous copy; [m_H | S_H | reward] come down without a copy where the
+    // rollout closes with the fused heads' k_glue (it stores them here: results_to_host), else in two; one host
     // synchronisation at the end (pageable buffers would cost a blocking staging copy per call)
     const size_t nst = (size_t)E + (size_t)E * E;
     if (ctx->pin_io_cap < 2 * nst + 8) {
@@ -666,9 +673,12 @@ static int rollout_begin(pilco_ctx* ctx, const pilco_policy* policy, const pilco
         HIPCHK(hipMemcpyAsync(plan.st[0], pin_in, sizeof(double) * nst, hipMemcpyHostToDevice, ctx->st));
         return PILCO_OK;
     };
+    plan.host_out = pin_out;   // (part of the graph key: a block that moved re-captures)
     if (int r = run_rollout(ctx, plan, H, upload)) return r;
-    HIPCHK(hipMemcpyAsync(pin_out, plan.st[H & 1], sizeof(double) * nst, hipMemcpyDeviceToHost, ctx->st));
-    HIPCHK(hipMemcpyAsync(pin_out + nst, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
+    if (!results_to_host(plan, H)) {
+        HIPCHK(hipMemcpyAsync(pin_out, plan.st[H & 1], sizeof(double) * nst, hipMemcpyDeviceToHost, ctx->st));
+        HIPCHK(hipMemcpyAsync(pin_out + nst, plan.g.reward, sizeof(double), hipMemcpyDeviceToHost, ctx->st));
+    }
     if (traj)
         HIPCHK(hipMemcpyAsync(traj, ctx->traj.p, sizeof(double) * (size_t)(H + 1) * (E + E * E), hipMemcpyDeviceToHost, ctx->st));
     rc.peer = plan.route.step == STEP_PEER;
@@ -1002,5 +1012,26 @@ int pilco_debug_geometry(pilco_ctx* ctx, int* out, int n) {
     const int v[PILCO_GEOMETRY_WORDS] = {s.npad, wk.PL, wk.EL, wk.NCH, wk.NCHM, wk.NT, wk.sk_waves, wk.sk_total, wk.sk_nd, wk.sk_maxw,
                                          sk_cap, device_cus_of(ctx->device), small_col_splits(ctx, s, true), small_col_splits(ctx, s, false)};
     for (int i = 0; i < std::min(n, (int)PILCO_GEOMETRY_WORDS); ++i) out[i] = v[i];
+    return PILCO_OK;
+}
+
+// test aid (pilco_debug_sk_cut_probe): the dynamics slot's stream-K cut as the device functions of the pair kernel give it
+int pilco_debug_sk_cut_probe(pilco_ctx* ctx, int* out, int n) {
+    if (!ctx || !out || n < PILCO_SK_PROBE_HEAD) return PILCO_E_SHAPE;
+    HIPCHK(hipSetDevice(ctx->device));
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    if (!s.wk_valid || s.wk.sk_waves <= 0) return fail(ctx, PILCO_E_STATE, "debug_sk_cut_probe: the dynamics slot has no stream-K cut (run a rollout with the stream-K pair kernel first)");
+    const MMWork& wk = s.wk;
+    const size_t words = (size_t)wk.sk_waves * PILCO_SK_PROBE_WORDS;
+    if ((size_t)n < PILCO_SK_PROBE_HEAD + words) return fail(ctx, PILCO_E_SHAPE, "debug_sk_cut_probe: the buffer is too small");
+    const int head[PILCO_SK_PROBE_HEAD] = {wk.sk_waves, wk.sk_nd, wk.sk_tdiag, wk.sk_toff, wk.sk_total, wk.sk_ud, wk.sk_uo, wk.PL, (int)wk.skm.fast, s.npad};
+    for (int i = 0; i < PILCO_SK_PROBE_HEAD; ++i) out[i] = head[i];
+    int* dev = nullptr;
+    HIPCHK(hipMalloc((void**)&dev, sizeof(int) * words));
+    launch_sk_cut_probe(ctx->st, model_of(s), wk, dev);
+    hipError_t e = hipMemcpyAsync(out + PILCO_SK_PROBE_HEAD, dev, sizeof(int) * words, hipMemcpyDeviceToHost, ctx->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->st);
+    (void)hipFree(dev);
+    HIPCHK(e);
     return PILCO_OK;
 }
