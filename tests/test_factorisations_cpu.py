@@ -9,6 +9,7 @@ import pytest
 import scipy.linalg as sla
 
 from helpers import fact_cases as fc
+from helpers.trtri_doubling import doubling as _doubling, trtri_levels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REQUIRED_NBLK = (1, 2, 3, 4, 5, 6, 7, 8, 9, 15, 16, 17, 31, 32, 33, 65)
@@ -25,16 +26,6 @@ KSPLIT = _header_const("FITC_KSPLIT")
 
 def _pad(n):
     return -(-n // NB) * NB
-
-
-def trtri_levels(npad):
-    """launch_trtri's sub-problems per level: (h, nsub, rows of the last sub-problem's lower half)."""
-    out, h = [], NB
-    while h < npad:
-        nsub = (npad - h + 2 * h - 1) // (2 * h)
-        out.append((h, nsub, (npad - h) - (nsub - 1) * 2 * h))
-        h *= 2
-    return out
 
 
 def ksplit_spans(Np):
@@ -199,27 +190,6 @@ def test_hp_factor_matches_lapack_on_well_conditioned_cases():
 
 
 # ---------------------------------------------------------------- sensitivity of the GPU criteria
-def _doubling(L, drop_clipped=False, perturb=None):
-    """L^{-1} by launch_trtri's recursive doubling on 64 x 64 blocks (float64).  drop_clipped: the last, clipped
-    sub-problem of the top level is skipped; perturb=(I, J, rel): tile (I, J) of the result scaled by 1 + rel."""
-    npad = L.shape[0]
-    X = np.zeros_like(L)
-    for b in range(0, npad, NB):
-        X[b:b + NB, b:b + NB] = sla.solve_triangular(L[b:b + NB, b:b + NB], np.eye(NB), lower=True)
-    for h, nsub, _ in trtri_levels(npad):
-        for q in range(nsub):
-            a0, b0 = q * 2 * h, q * 2 * h + h
-            b1 = min(b0 + h, npad)
-            if drop_clipped and h == trtri_levels(npad)[-1][0] and q == nsub - 1 and b1 - b0 < h:
-                continue
-            T = L[b0:b1, a0:b0] @ X[a0:b0, a0:b0]
-            X[b0:b1, a0:b0] = -X[b0:b1, b0:b1] @ T
-    if perturb:
-        I, J, rel = perturb
-        X[I * NB:(I + 1) * NB, J * NB:(J + 1) * NB] *= 1 + rel
-    return X
-
-
 def _emulate(d, a, **kw):
     from oracle import hp_factor as hp
     N = len(d["X"])
