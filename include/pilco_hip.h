@@ -222,6 +222,32 @@ int pilco_rollout_particles_events(pilco_ctx* ctx, const pilco_policy* policy, c
                                    const double* x0, int P, int H, const double* eps, unsigned long long seed,
                                    int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
                                    double* eps_out, const pilco_event* events, int n_events, long long* counts, int* first_hit);
+/* Value and pathwise gradient of the particle return (extension; docs/particle_gradients.md).  With x0 and the draws fixed
+ * (eps given, or the Philox stream of seed exactly as pilco_rollout_particles generates it), J = sum_t (1/P) sum_p r(x_t^p)
+ * over the PRE-step states t = 0..H-1 is a smooth function of the controller parameters.  reward = J, the sum in step order of
+ * reward_steps (H, may be NULL), which has the bits of pilco_rollout_particles on the same inputs.  dW (U,E), db (U): dJ / d
+ * (W, b) of a LinearController; ignored (may be NULL) for PILCO_POLICY_NONE.  dreturn_dx0 (P,E), may be NULL: row p is the
+ * gradient of particle p's OWN return sum_t r(x_t^p) w.r.t. its x0 row (not divided by P); it has the same bits alone or in any
+ * batch.  The derivative through the clamp sqrt(max(v, 0)) is 0 where v <= 0.
+ * The forward pass stores one (E, D) step matrix per particle and step t < H-1; above a budget (1 GiB; the environment's
+ * PILCO_PARTICLE_GRAD_BUDGET, in doubles, read at every call) the particles run in groups of a multiple of 128, one after the
+ * other.  The parameter sums run in a fixed order without floating-point atomics (particles in index order inside blocks of
+ * 128 per step, the steps t = H-2..0 added to the block's cell, the cells in block order, one division by P): neither the
+ * chunks nor the groups change a bit of any output.  One upload; one download and synchronisation per group and one at the end.
+ * Refuses what pilco_rollout_particles refuses, a null reward, a policy kind other than NONE / LINEAR, and a null dW or db for
+ * a LinearController -- all before any launch or upload, the outputs untouched. */
+int pilco_rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                 const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
+                                 double* reward, double* reward_steps, double* dW, double* db, double* dreturn_dx0);
+/* The same for an RbfController whose GP lives in PILCO_SLOT_POLICY: gradients w.r.t. the centres Xp (bf,E), the targets Yp
+ * (bf,U) and the lengthscales lsp (U,E); the caller passes the host copies of the parameters it uploaded, as for
+ * pilco_rollout_grad_rbf (noisep (U)).  Also refuses null Xp / Yp / lsp / noisep / dX / dY / dls, a bf that is not the policy
+ * slot's number of points, and (PILCO_E_NOT_PD) a singular K + noise I. */
+int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                     const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                     int observation_noise, const double* Xp, const double* Yp, const double* lsp,
+                                     const double* noisep, int bf, double* reward, double* reward_steps, double* dX, double* dY,
+                                     double* dls, double* dreturn_dx0);
 
 /* ------------------------------------------------------------------ reverse mode
  * The reference differentiates training_loss with TensorFlow's autodiff (pilco/models/pilco.py:85-90);

@@ -102,6 +102,11 @@ SIGNATURES = {
     "pilco_rollout_particles_events": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
                                                  _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp,
                                                  C.POINTER(Event), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "pilco_rollout_particles_grad": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                               _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles_grad_rbf": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                                   _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
+                                                   _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_gp_predict_vjp": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout_tape": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                      _dp, _dp, _dp, _dp, _dp]),
@@ -503,6 +508,49 @@ class Context:
         self._chk(self.lib.pilco_rollout_particles_events(*args, ev, K, counts.ctypes.data_as(C.POINTER(C.c_longlong)),
                                                           first.ctypes.data_as(C.POINTER(C.c_int))))
         return mean, cov, rew, parts, used, counts, first
+
+    def _particle_grad_args(self, policy, rewards, x0, H, eps, seed, observation_noise):
+        E = policy["state_dim"]
+        p, k1 = self._policy(policy)
+        r, k2 = self._rewards(rewards, E)
+        x0 = _f64(x0)
+        if x0.ndim != 2 or x0.shape[1] != E:
+            raise ValueError(f"initial particles must be (P, {E})")
+        P, H = x0.shape[0], int(H)
+        if eps is not None:
+            eps = _f64(eps)
+            if eps.shape != (H, P, E):
+                raise ValueError(f"draws must be ({H}, {P}, {E})")
+        head = (self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                1 if observation_noise else 0)
+        return head, (p, k1, r, k2, x0, eps), P, H
+
+    def rollout_particles_grad(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_dx0=False):
+        """Value and pathwise gradient of the particle return J = reward_steps.sum() of rollout_particles on the same x0 and
+        draws (pilco_rollout_particles_grad; docs/particle_gradients.md), for no policy or a LinearController.  Returns
+        (reward, reward_steps (H,), dW (U, E), db (U,), dreturn_dx0 (P, E) or None); dreturn_dx0[p] is the gradient of particle
+        p's own return, not divided by P."""
+        E, U = policy["state_dim"], policy["control_dim"]
+        head, keep, P, H = self._particle_grad_args(policy, rewards, x0, H, eps, seed, observation_noise)
+        rew = np.zeros((1,)); steps = np.empty((max(H, 0),)); dW = np.zeros((U, E)); db = np.zeros((U,))
+        dx0 = np.empty((P, E)) if want_dx0 else None
+        self._chk(self.lib.pilco_rollout_particles_grad(*head, _ptr(rew), _ptr(steps), _ptr(dW), _ptr(db), _ptr(dx0)))
+        return float(rew[0]), steps, dW, db, dx0
+
+    def rollout_particles_grad_rbf(self, policy, rewards, x0, H, Xp, Yp, lsp, noisep, eps=None, seed=0, observation_noise=False,
+                                   want_dx0=False):
+        """The same for an RbfController (pilco_rollout_particles_grad_rbf): (reward, reward_steps, dX (bf, E), dY (bf, U),
+        dls (U, E), dreturn_dx0 or None)."""
+        E, U = policy["state_dim"], policy["control_dim"]
+        head, keep, P, H = self._particle_grad_args(policy, rewards, x0, H, eps, seed, observation_noise)
+        Xp = _f64(Xp); bf = Xp.shape[0]
+        Xp = _f64(Xp, (bf, E)); Yp = _f64(Yp, (bf, U)); lsp = _f64(lsp, (U, E)); noisep = _f64(noisep, (U,))
+        rew = np.zeros((1,)); steps = np.empty((max(H, 0),))
+        dX = np.empty((bf, E)); dY = np.empty((bf, U)); dls = np.empty((U, E))
+        dx0 = np.empty((P, E)) if want_dx0 else None
+        self._chk(self.lib.pilco_rollout_particles_grad_rbf(*head, _ptr(Xp), _ptr(Yp), _ptr(lsp), _ptr(noisep), bf, _ptr(rew),
+                                                            _ptr(steps), _ptr(dX), _ptr(dY), _ptr(dls), _ptr(dx0)))
+        return float(rew[0]), steps, dX, dY, dls, dx0
 
     def particle_actions(self, policy, x):
         """Test aid: the actions (P, U) the particle rollout acts with at the states x (P, E) (pilco_debug_particle_actions)."""

@@ -2,6 +2,7 @@
 // (DESIGN.md section 9).
 #include "ctx.h"
 #include "reward_factor.h"
+#include "rbf_solve_adj.h"
 
 extern "C" {
 
@@ -324,29 +325,22 @@ struct LinearAdj : PolicyAdj {
 // S -= diag(var - 1e-6)): the same line-by-line reverse as pilco_amd/adjoint.py (rbf_policy_fwd / rbf_policy_vjp), which
 // is checked against autograd on the CPU (tests/test_oracle.py); beta = (K + noise I)^-1 Y and the Gram matrices do not
 // change along the sweep, so their cotangent is accumulated and pushed through the solve once at the end.
-struct RbfAdj : PolicyAdj {
+// The solve beta_k = (K_k + noise_k I)^-1 Y_k of the policy GP and its adjoint: what the reverse sweep below and the particle
+// gradient (particles_grad.hip, through rbf_solve_adj.h) share.
+struct RbfSolve {
     int n, d, U;
     Mat X, Y, ls;
     vec noise;
     std::vector<Mat> K, Ainv;
     Mat beta;                         // (U, n)
-    Mat Xbar, lsbar, bbsum;           // accumulated cotangents of X (direct part), ls (direct part) and beta
-    // per-step cache
-    Mat zeta;
-    vec Mv;
-    struct MeanC { Mat T, G; vec ex, q; };
-    struct PairC { Mat z, w, Ri, Q, zQ, wQ, L; double r, val; };
-    std::vector<MeanC> mean;
-    std::vector<PairC> pair;
-    vec s_cur;
-    bool init(int n_, int d_, int U_, const double* Xp, const double* Yp, const double* lsp, const double* nz) {
+    bool solve(int n_, int d_, int U_, const double* Xp, const double* Yp, const double* lsp, const double* nz) {
         n = n_; d = d_; U = U_;
         X = Mat(n, d); Y = Mat(n, U); ls = Mat(U, d);
         X.d.assign(Xp, Xp + (size_t)n * d);
         Y.d.assign(Yp, Yp + (size_t)n * U);
         ls.d.assign(lsp, lsp + (size_t)U * d);
         noise.assign(nz, nz + U);
-        beta = Mat(U, n); Xbar = Mat(n, d); lsbar = Mat(U, d); bbsum = Mat(U, n);
+        beta = Mat(U, n);
         K.resize(U); Ainv.resize(U);
         for (int a = 0; a < U; ++a) {
             K[a] = Mat(n, n);
@@ -370,6 +364,49 @@ struct RbfAdj : PolicyAdj {
                 beta(a, i) = acc;
             }
         }
+        return true;
+    }
+    // the cotangent bbsum (U, n) of beta through the solve, on top of the direct parts Xbar (n, d) and lsbar (U, d)
+    void solve_adjoint(const Mat& Xbar, const Mat& lsbar, const Mat& bbsum, double* dX, double* dY, double* dls) const {
+        Mat Xb = Xbar, lb = lsbar, Yb(n, U);
+        for (int a = 0; a < U; ++a) {
+            vec g(n, 0.0);
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) g[i] += Ainv[a](i, j) * bbsum(a, j);      // Ainv symmetric
+            Mat Wk(n, n);
+            for (int i = 0; i < n; ++i) {
+                Yb(i, a) = g[i];
+                for (int j = 0; j < n; ++j) Wk(i, j) = -g[i] * beta(a, j) * K[a](i, j);
+            }
+            for (int i = 0; i < n; ++i)
+                for (int j = 0; j < n; ++j) {
+                    const double wsym = Wk(i, j) + Wk(j, i);
+                    for (int k = 0; k < d; ++k) {
+                        const double df = X(i, k) - X(j, k);
+                        Xb(i, k) -= wsym * df / (ls(a, k) * ls(a, k));
+                        lb(a, k) += 0.5 * wsym * df * df / (ls(a, k) * ls(a, k) * ls(a, k));
+                    }
+                }
+        }
+        memcpy(dX, Xb.d.data(), sizeof(double) * n * d);
+        memcpy(dY, Yb.d.data(), sizeof(double) * n * U);
+        memcpy(dls, lb.d.data(), sizeof(double) * U * d);
+    }
+};
+
+struct RbfAdj : PolicyAdj, RbfSolve {
+    Mat Xbar, lsbar, bbsum;           // accumulated cotangents of X (direct part), ls (direct part) and beta
+    // per-step cache
+    Mat zeta;
+    vec Mv;
+    struct MeanC { Mat T, G; vec ex, q; };
+    struct PairC { Mat z, w, Ri, Q, zQ, wQ, L; double r, val; };
+    std::vector<MeanC> mean;
+    std::vector<PairC> pair;
+    vec s_cur;
+    bool init(int n_, int d_, int U_, const double* Xp, const double* Yp, const double* lsp, const double* nz) {
+        if (!solve(n_, d_, U_, Xp, Yp, lsp, nz)) return false;
+        Xbar = Mat(n, d); lsbar = Mat(U, d); bbsum = Mat(U, n);
         mean.resize(U);
         pair.resize((size_t)U * U);
         return true;
@@ -565,31 +602,7 @@ struct RbfAdj : PolicyAdj {
         for (size_t e = 0; e < bbsum.d.size(); ++e) bbsum.d[e] += bb.d[e];
     }
     // push the accumulated cotangent of beta through beta = (K + noise I)^-1 Y (once, after the sweep)
-    void finish(double* dX, double* dY, double* dls) {
-        Mat Xb = Xbar, lb = lsbar, Yb(n, U);
-        for (int a = 0; a < U; ++a) {
-            vec g(n, 0.0);
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j < n; ++j) g[i] += Ainv[a](i, j) * bbsum(a, j);      // Ainv symmetric
-            Mat Wk(n, n);
-            for (int i = 0; i < n; ++i) {
-                Yb(i, a) = g[i];
-                for (int j = 0; j < n; ++j) Wk(i, j) = -g[i] * beta(a, j) * K[a](i, j);
-            }
-            for (int i = 0; i < n; ++i)
-                for (int j = 0; j < n; ++j) {
-                    const double wsym = Wk(i, j) + Wk(j, i);
-                    for (int k = 0; k < d; ++k) {
-                        const double df = X(i, k) - X(j, k);
-                        Xb(i, k) -= wsym * df / (ls(a, k) * ls(a, k));
-                        lb(a, k) += 0.5 * wsym * df * df / (ls(a, k) * ls(a, k) * ls(a, k));
-                    }
-                }
-        }
-        memcpy(dX, Xb.d.data(), sizeof(double) * n * d);
-        memcpy(dY, Yb.d.data(), sizeof(double) * n * U);
-        memcpy(dls, lb.d.data(), sizeof(double) * U * d);
-    }
+    void finish(double* dX, double* dY, double* dls) { solve_adjoint(Xbar, lsbar, bbsum, dX, dY, dls); }
 };
 
 // The reverse sweep common to both policies: propagate (pilco.py:147-149), joint Gaussian (:141-144), squash
@@ -787,6 +800,20 @@ int check_grad_args(pilco_ctx* ctx, const pilco_policy* policy, const pilco_rewa
 }
 
 }  // namespace
+
+// rbf_solve_adj.h
+bool rbf_solve_adjoint(int bf, int E, int U, const double* Xp, const double* Yp, const double* lsp, const double* noisep,
+                       const double* Xbar, const double* lsbar, const double* betabar, double* dX, double* dY, double* dls) {
+    RbfSolve sv;
+    if (!sv.solve(bf, E, U, Xp, Yp, lsp, noisep)) return false;
+    if (!betabar) return true;
+    Mat Xb(bf, E), lb(U, E), bb(U, bf);
+    Xb.d.assign(Xbar, Xbar + Xb.d.size());
+    lb.d.assign(lsbar, lsbar + lb.d.size());
+    bb.d.assign(betabar, betabar + bb.d.size());
+    sv.solve_adjoint(Xb, lb, bb, dX, dY, dls);
+    return true;
+}
 
 extern "C" {
 

@@ -22,21 +22,10 @@
 //   k_particle_events / k_particle_events_finish   per event the number of particles that hit it, and every particle's first hit
 // Integer counts: a block of PT_BLOCK particles counts by wave ballot, the blocks' counts are added in block order; no atomics.
 #include "particle_events.h"
+#include "particles.h"
 #include "philox_normal.h"
-#include "predict.h"
 
 namespace pilco {
-
-constexpr int PT_BLOCK = 128;
-
-struct ParticleHeadArgs {
-    const double* x;   // [P][E] the step's states
-    double* Xt;        // [D][ldt] the chunk's test points [x, u], transposed; zero past ntc
-    int p0, ntc, ldt, E, U, kind, squash;
-    const double *W, *b, *maxact;             // LinearController [U][E], [U]; scale of the squash [U]
-    const double *pc, *pls, *pvar, *pbeta;    // RbfController (policy slot): centres [E][pnpad], lengthscales [U][E], variances [U], beta [U][pnpad]
-    int pn, pnpad;
-};
 
 __global__ __launch_bounds__(256) void k_particle_head(ParticleHeadArgs a) {
     const int E = a.E, U = a.U, ldt = a.ldt;
@@ -72,25 +61,6 @@ __global__ __launch_bounds__(256) void k_particle_head(ParticleHeadArgs a) {
         a.Xt[(long)(E + k) * ldt + i] = a.squash ? scale * sin(s) : s;
     }
 }
-
-struct ParticleReward {
-    int kind;
-    double coef;
-    const double *W, *t;   // exponential: [E][E], [E]; linear: [E]
-};
-
-struct ParticleTailArgs {
-    const double* x;        // [P][E] the step's states
-    double* xn;             // [P][E] the next states
-    const double *mu, *var; // [E][ldt] posterior of the chunk
-    const double* noise;    // [E] likelihood variances (observation_noise), or nullptr
-    const double* eps_in;   // [P][E] the step's draws, or nullptr: generated here
-    double* eps_out;        // [P][E] the draws used, or nullptr
-    double* rew;            // [P] reward of the pre-step state
-    unsigned long long seed;
-    int t, p0, ntc, ldt, E, n_rewards;
-    ParticleReward rw[MAX_REWARD_TERMS];
-};
 
 __device__ __forceinline__ double particle_reward(const ParticleTailArgs& a, const double* xr) {
     const int E = a.E;
@@ -238,15 +208,15 @@ __global__ __launch_bounds__(64) void k_particle_events_finish(ParticleEventArgs
 
 using namespace pilco;
 
-namespace {
-struct StreamDrain {   // the staging vectors of the call are locals: nothing of the stream may outlive them
-    hipStream_t st;
-    ~StreamDrain() { (void)hipStreamSynchronize(st); }
-};
-}  // namespace
+void launch_particle_head(hipStream_t st, const ParticleHeadArgs& a) {
+    hipLaunchKernelGGL(k_particle_head, dim3((a.ldt + 255) / 256), dim3(256), 0, st, a);
+}
+void launch_particle_tail(hipStream_t st, const ParticleTailArgs& a) {
+    hipLaunchKernelGGL(k_particle_tail, dim3((a.ntc + 255) / 256), dim3(256), 0, st, a);
+}
 
 // the policy against the dynamics slot (and, RbfController, the policy slot)
-static int check_policy(pilco_ctx* ctx, const pilco_policy* policy) {
+int check_policy(pilco_ctx* ctx, const pilco_policy* policy) {
     const Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
     if (!policy) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: null policy");
     const int E = s.E, D = s.D, U = D - E;
@@ -266,8 +236,8 @@ static int check_policy(pilco_ctx* ctx, const pilco_policy* policy) {
 }
 
 // the policy's parameters into the staging vector hp (W[U*E] b[U] maxact[U]) and the action kernel's arguments; dev: where hp goes
-static void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double>& hp, size_t& off, const double* dev,
-                         ParticleHeadArgs& ha) {
+void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double>& hp, size_t& off, const double* dev,
+                  ParticleHeadArgs& ha) {
     const Slot &s = ctx->slot[PILCO_SLOT_DYNAMICS], &ps = ctx->slot[PILCO_SLOT_POLICY];
     const int E = s.E, U = s.D - s.E;
     ha.E = E; ha.U = U; ha.kind = policy->kind; ha.squash = policy->squash;
@@ -285,11 +255,8 @@ static void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector
     }
 }
 
-// pilco_rollout_particles and pilco_rollout_particles_events: with n_events == 0 exactly the launches of the former
-static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
-                             const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
-                             double* mean, double* cov, double* reward_steps, double* particles, double* eps_out,
-                             const pilco_event* events, int n_events, long long* counts, int* first_hit) {
+// what pilco_rollout_particles refuses about the slot, the context, P and H
+int check_particle_state(pilco_ctx* ctx, int P, int H) {
     if (int r = check_slot(ctx, PILCO_SLOT_DYNAMICS)) return r;
     Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
     if (ctx->nranks != 1 || ctx->comm || s.shW > 1) return fail(ctx, PILCO_E_STATE, "rollout_particles: single rank only");
@@ -297,9 +264,12 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
     if (s.user_factors)
         return fail(ctx, PILCO_E_STATE, "rollout_particles: the slot holds factors set by pilco_gp_set_factors, not its own factorisation");
     if (P <= 0 || H < 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: P must be positive and H non-negative");
-    if (!x0 || !mean || !cov) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: null x0, mean or cov");
+    return PILCO_OK;
+}
+
+// ... and about the policy and the reward terms
+int check_particle_terms(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards) {
     if (int r = check_policy(ctx, policy)) return r;
-    const int E = s.E, D = s.D, U = D - E;
     if (n_rewards < 0 || n_rewards > MAX_REWARD_TERMS || (n_rewards > 0 && !rewards))
         return fail(ctx, PILCO_E_SHAPE, "rollout_particles: 0..4 reward terms supported");
     for (int i = 0; i < n_rewards; ++i) {
@@ -307,6 +277,39 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
             return fail(ctx, PILCO_E_SHAPE, "reward: unknown kind");
         if (!rewards[i].W) return fail(ctx, PILCO_E_SHAPE, "reward: W is required");
     }
+    return PILCO_OK;
+}
+
+// the reward terms into the staging vector hp and the draw kernel's arguments; dev: where hp goes
+void stage_rewards(const pilco_reward_term* rewards, int n_rewards, int E, std::vector<double>& hp, size_t& off, const double* dev,
+                   ParticleReward* rw) {
+    for (int i = 0; i < n_rewards; ++i) {
+        ParticleReward& r = rw[i];
+        r.kind = rewards[i].kind;
+        r.coef = rewards[i].coef;
+        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
+            memcpy(&hp[off], rewards[i].W, sizeof(double) * E * E);
+            r.W = dev + off; off += (size_t)E * E;
+            if (rewards[i].t) memcpy(&hp[off], rewards[i].t, sizeof(double) * E);   // (NULL: the zeros hp holds)
+            r.t = dev + off; off += E;
+        } else {
+            memcpy(&hp[off], rewards[i].W, sizeof(double) * E);
+            r.W = dev + off; off += E;
+            r.t = r.W;
+        }
+    }
+}
+
+// pilco_rollout_particles and pilco_rollout_particles_events: with n_events == 0 exactly the launches of the former
+static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                             const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
+                             double* mean, double* cov, double* reward_steps, double* particles, double* eps_out,
+                             const pilco_event* events, int n_events, long long* counts, int* first_hit) {
+    if (int r = check_particle_state(ctx, P, H)) return r;
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    if (!x0 || !mean || !cov) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: null x0, mean or cov");
+    if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
+    const int E = s.E, D = s.D, U = D - E;
     if (const char* why = event_table_refusal(events, n_events, counts, E))
         return fail(ctx, PILCO_E_SHAPE, std::string("rollout_particles: ") + why);
     HIPCHK(hipSetDevice(ctx->device));
@@ -323,7 +326,7 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
     const int nslab = particles ? H + 1 : 2;
     const bool keep_eps = H > 0 && (eps || eps_out);
     // parameters: W[U*E] b[U] maxact[U], then per reward W[E*E] t[E] (exponential) or W[E] (linear)
-    std::vector<double> hp((size_t)U * E + 2 * U + (size_t)MAX_REWARD_TERMS * (E * E + E) + 8, 0.0);
+    std::vector<double> hp(particle_par_doubles(E, U), 0.0);
     std::vector<double> hstats((size_t)(H + 1) * Q);
     ENSURE(pw.Xt, (size_t)D * ntc_max);
     ENSURE(pw.Ks, (size_t)E * ntc_max * npad);
@@ -348,21 +351,7 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
     size_t off = 0;
     stage_policy(ctx, policy, hp, off, pw.pt_par.p, ha);
     ta.n_rewards = n_rewards;
-    for (int i = 0; i < n_rewards; ++i) {
-        ParticleReward& r = ta.rw[i];
-        r.kind = rewards[i].kind;
-        r.coef = rewards[i].coef;
-        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
-            memcpy(&hp[off], rewards[i].W, sizeof(double) * E * E);
-            r.W = pw.pt_par.p + off; off += (size_t)E * E;
-            if (rewards[i].t) memcpy(&hp[off], rewards[i].t, sizeof(double) * E);   // (NULL: the zeros hp holds)
-            r.t = pw.pt_par.p + off; off += E;
-        } else {
-            memcpy(&hp[off], rewards[i].W, sizeof(double) * E);
-            r.W = pw.pt_par.p + off; off += E;
-            r.t = r.W;
-        }
-    }
+    stage_rewards(rewards, n_rewards, E, hp, off, pw.pt_par.p, ta.rw);
     StreamDrain drain{st};
     // one upload: parameters, initial particles, the caller's draws
     HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
@@ -410,10 +399,10 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
             const int ntc = std::min(ntc_max, P - p0), ldt = round_up(ntc, 64);
             double *out_mean = pw.out.p, *out_var = pw.out.p + (size_t)E * ldt;
             ha.Xt = pw.Xt.p; ha.p0 = p0; ha.ntc = ntc; ha.ldt = ldt;
-            hipLaunchKernelGGL(k_particle_head, dim3((ldt + 255) / 256), dim3(256), 0, st, ha);
+            launch_particle_head(st, ha);
             if (int r = predict_points_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, out_mean, out_var)) return r;
             ta.mu = out_mean; ta.var = out_var; ta.p0 = p0; ta.ntc = ntc; ta.ldt = ldt;
-            hipLaunchKernelGGL(k_particle_tail, dim3((ntc + 255) / 256), dim3(256), 0, st, ta);
+            launch_particle_tail(st, ta);
         }
         stats(t + 1, true);   // (its reward word: the mean reward of the pre-step states of step t)
         count_events(t + 1);

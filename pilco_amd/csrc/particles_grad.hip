@@ -1,0 +1,468 @@
+// Policy gradients through particle rollouts: pilco_rollout_particles_grad / _grad_rbf.  docs/particle_gradients.md.
+// With fixed initial particles and fixed draws the particle return J = sum_t (1/P) sum_p r(x_t^p) is a smooth function of the
+// controller parameters; this is its pathwise (reparameterisation) gradient, by a reverse sweep over stored step matrices.
+//
+// FORWARD, per step t and per chunk of particles: the launches of pilco_rollout_particles (k_particle_head,
+// predict_points_device, k_particle_tail: the same states and rewards, bit for bit) and, for t < H - 1,
+//   predict_points_jac_device (predict_jac.hip)   d mu / d z, d v / d z at z = [x, u]: two launches
+//   k_pg_fold        A_t[e][d] = [e == d] + d mu_e / d z_d + g_e d v_e / d z_d,  g_e = eps_e / (2 sd_e) where v~_e > 0, else 0,
+//                    stored [t][e][d][particle]: the particle index fastest
+//   k_pg_reward_partials   the blocks' reward sums of the step (the sums of k_particle_partials)
+// REVERSE, t = H-1 .. 0, one launch over the group's particles, one thread per particle, its vectors parked in LDS:
+//   k_pg_reverse     g_u = A[:, E:]^T lam,  ds_k = g_u[k] scale_k cos(s_k),  lam' = A[:, :E]^T lam + (ds/dx)^T ds + grad r(x_t)
+//                    (step H - 1 meets lam_H = 0: its matrix is neither computed nor read)
+//   k_pg_param_partials   (t <= H - 2) per block of PT_BLOCK particles and per parameter the block's sum, added to the block's cell
+// and after the last group  k_pg_finish: the blocks' cells in block order, divided by P.
+//
+// ORDER OF THE PARAMETER SUMS (no floating-point atomics): the particles are cut into blocks of PT_BLOCK = 128 consecutive
+// indices; one thread per quantity adds a block's particles of one step in index order (from zero) and adds that sum to the
+// block's cell, steps in the order t = H-2 .. 0; the blocks' cells are added in block order; one division by P.  The reward sums
+// are those of pilco_rollout_particles.  Neither depends on the chunks or on the groups.
+//
+// GROUPS: the stored matrices take (H-1) P E D doubles.  Above the budget (PG_BUDGET doubles; PILCO_PARTICLE_GRAD_BUDGET in the
+// environment, read at every call) the particles run in groups of a multiple of PT_BLOCK particles, each forward then reverse;
+// the particles are independent and a block never straddles two groups, so every output has the bits of the one-group run.
+#include "particles.h"
+#include "rbf_solve_adj.h"
+
+namespace pilco {
+
+constexpr size_t PG_BUDGET = size_t(1) << 27;   // doubles of stored step matrices per group (1 GiB)
+constexpr int PG_RB = 64;                       // particles (threads) per workgroup of the reverse kernel
+
+struct PgFoldArgs {
+    const double *dmean, *dvar;   // [E][ldt][D] of the chunk
+    const double* var;            // [E][ldt]
+    const double* noise;          // [E] or nullptr
+    const double* eps;            // [P][E] the step's draws
+    double* A;                    // [E][D][ldg] the step's matrices of the group
+    int p0, l0, ntc, ldt, ldg, E, D;   // p0: first particle of the chunk, l0: its index in the group
+};
+
+// thread (i, e): row e of particle i's step matrix
+__global__ __launch_bounds__(256) void k_pg_fold(PgFoldArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x, e = blockIdx.y;
+    if (i >= a.ntc) return;
+    const int D = a.D;
+    double v = a.var[(long)e * a.ldt + i];
+    if (a.noise) v += a.noise[e];
+    // the clamp sd = sqrt(max(v, 0)) has no derivative at v <= 0
+    const double g = v > 0.0 ? a.eps[(long)(a.p0 + i) * a.E + e] / (2.0 * sqrt(v)) : 0.0;
+    const double* dm = a.dmean + ((long)e * a.ldt + i) * D;
+    const double* dv = a.dvar + ((long)e * a.ldt + i) * D;
+    double* A = a.A + (long)e * D * a.ldg + a.l0 + i;
+    for (int d = 0; d < D; ++d) A[(long)d * a.ldg] = fma(g, dv[d], dm[d] + (d == e ? 1.0 : 0.0));
+}
+
+// thread b: the reward sum of block b0 + b at step t, the particles in index order (zeros past P, as k_particle_partials).
+// part [blocks][H]
+__global__ __launch_bounds__(64) void k_pg_reward_partials(const double* rew, double* part, int P, int b0, int nb, int t, int H) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nb) return;
+    const long p0 = (long)(b0 + b) * PT_BLOCK;
+    double s = 0.0;
+    for (int k = 0; k < PT_BLOCK; ++k) s += (p0 + k < P) ? rew[p0 + k] : 0.0;
+    part[(long)(b0 + b) * H + t] = s;
+}
+
+struct PgReverseArgs {
+    ParticleHeadArgs pol;   // the policy (x: the states of step t, [P][E]; p0: the group's first particle; ntc: its particles)
+    const double* A;        // [E][D][ldg] the step's matrices, or nullptr: lam_in is zero (t = H - 1)
+    const double* lam_in;   // [E][ldg]
+    double* lam_out;        // [E][ldg]
+    double* ds;             // [U][ldg] cotangents of the sines' arguments
+    int ldg, n_rewards;
+    ParticleReward rw[MAX_REWARD_TERMS];
+};
+
+// dynamic LDS: [3 E + U][PG_RB] the particle's lam, x, lam' and g_u / ds (a column per thread), then 1 / lengthscale [U][E]
+inline int pg_reverse_lds_doubles(int E, int U) { return (3 * E + U) * PG_RB + U * E; }
+
+__global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) {
+    extern __shared__ double pg_lds[];
+    const ParticleHeadArgs& po = a.pol;
+    const int E = po.E, U = po.U, D = E + U, tid = threadIdx.x, ldg = a.ldg;
+    double* lam = pg_lds + tid;               // element e: lam[e * PG_RB]
+    double* xs = lam + E * PG_RB;
+    double* ln = xs + E * PG_RB;
+    double* du = ln + E * PG_RB;
+    double* il_s = pg_lds + (3 * E + U) * PG_RB;
+    if (po.kind == PILCO_POLICY_RBF)
+        for (int q = tid; q < U * E; q += PG_RB) il_s[q] = 1.0 / po.pls[q];
+    __syncthreads();
+    const int l = blockIdx.x * PG_RB + tid;
+    if (l >= po.ntc) return;
+    const double* xr = po.x + (long)(po.p0 + l) * E;
+    for (int e = 0; e < E; ++e) xs[e * PG_RB] = xr[e];
+    if (a.A) {
+        for (int e = 0; e < E; ++e) lam[e * PG_RB] = a.lam_in[(long)e * ldg + l];
+        const double* A = a.A + l;
+        for (int d = 0; d < D; ++d) {
+            double acc = 0.0;
+            for (int e = 0; e < E; ++e) acc = fma(A[((long)e * D + d) * ldg], lam[e * PG_RB], acc);
+            if (d < E) ln[d * PG_RB] = acc; else du[(d - E) * PG_RB] = acc;
+        }
+    } else {
+        for (int e = 0; e < E; ++e) ln[e * PG_RB] = 0.0;
+        for (int k = 0; k < U; ++k) du[k * PG_RB] = 0.0;
+    }
+    // the policy: ds_k = g_u[k] d u_k / d s_k, lam' += (ds / dx)^T ds
+    for (int k = 0; k < U; ++k) {
+        const double gu = du[k * PG_RB];
+        double dsk = gu;
+        if (po.kind == PILCO_POLICY_LINEAR) {
+            if (po.squash) {
+                double s = 0.0;
+                for (int e = 0; e < E; ++e) s = fma(xs[e * PG_RB], po.W[k * E + e], s);
+                s += po.b[k];
+                dsk = gu * (po.maxact[k] * cos(s));
+            }
+            for (int e = 0; e < E; ++e) ln[e * PG_RB] = fma(po.W[k * E + e], dsk, ln[e * PG_RB]);
+        } else if (po.kind == PILCO_POLICY_RBF) {
+            const double vk = po.pvar[k];
+            if (po.squash) {
+                double s = 0.0;
+                for (int c = 0; c < po.pn; ++c) {
+                    double r2 = 0.0;
+                    for (int e = 0; e < E; ++e) {
+                        const double d = (xs[e * PG_RB] - po.pc[(long)e * po.pnpad + c]) * il_s[k * E + e];
+                        r2 = fma(d, d, r2);
+                    }
+                    s = fma(po.pbeta[(long)k * po.pnpad + c], vk * exp(-0.5 * r2), s);
+                }
+                dsk = gu * (po.maxact[k] * exp(-0.5e-6) * cos(s));
+            }
+            for (int c = 0; c < po.pn; ++c) {
+                double r2 = 0.0;
+                for (int e = 0; e < E; ++e) {
+                    const double d = (xs[e * PG_RB] - po.pc[(long)e * po.pnpad + c]) * il_s[k * E + e];
+                    r2 = fma(d, d, r2);
+                }
+                const double w = dsk * po.pbeta[(long)k * po.pnpad + c] * (vk * exp(-0.5 * r2));
+                for (int e = 0; e < E; ++e) {
+                    const double il = il_s[k * E + e];
+                    ln[e * PG_RB] = fma(-w, (xs[e * PG_RB] - po.pc[(long)e * po.pnpad + c]) * (il * il), ln[e * PG_RB]);
+                }
+            }
+        }
+        a.ds[(long)k * ldg + l] = dsk;
+    }
+    // the reward of the pre-step state: exponential grad r = -r/2 (W + W^T)(x - t), linear grad r = W
+    for (int k = 0; k < a.n_rewards; ++k) {
+        const ParticleReward& r = a.rw[k];
+        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
+            double q = 0.0;
+            for (int i = 0; i < E; ++i) {
+                double row = 0.0;
+                for (int j = 0; j < E; ++j) row = fma(r.W[i * E + j], xs[j * PG_RB] - r.t[j], row);
+                q = fma(xs[i * PG_RB] - r.t[i], row, q);
+            }
+            const double c = -0.5 * r.coef * exp(-0.5 * q);
+            for (int i = 0; i < E; ++i) {
+                double row = 0.0;
+                for (int j = 0; j < E; ++j) row = fma(r.W[i * E + j] + r.W[j * E + i], xs[j * PG_RB] - r.t[j], row);
+                ln[i * PG_RB] = fma(c, row, ln[i * PG_RB]);
+            }
+        } else {
+            for (int i = 0; i < E; ++i) ln[i * PG_RB] = fma(r.coef, r.W[i], ln[i * PG_RB]);
+        }
+    }
+    for (int e = 0; e < E; ++e) a.lam_out[(long)e * ldg + l] = ln[e * PG_RB];
+}
+
+struct PgParamArgs {
+    ParticleHeadArgs pol;   // as PgReverseArgs
+    const double* ds;       // [U][ldg]
+    double* part;           // [blocks of all particles][Q] the blocks' cells
+    int ldg, Q;
+};
+
+// quantities of a policy: LinearController dW [U][E] | db [U]; RbfController dbeta [U][bf] | dC [bf][E] | dl [U][E]
+inline int pg_quantities(int kind, int E, int U, int bf) { return kind == PILCO_POLICY_RBF ? U * bf + bf * E + U * E : U * E + U; }
+
+// block b of the group: particles PT_BLOCK b .. ; thread q adds quantity q over them in index order
+__global__ __launch_bounds__(PT_BLOCK) void k_pg_param_partials(PgParamArgs a) {
+    const ParticleHeadArgs& po = a.pol;
+    const int E = po.E, U = po.U, Q = a.Q, bf = po.pn;
+    __shared__ double sh[PT_BLOCK * MAX_D];        // [particle][x] then [particle][ds]
+    __shared__ double il_s[MAX_D * MAX_D / 4];     // RbfController: 1 / lengthscale [U][E]  (U + E <= MAX_D)
+    double* xs = sh;
+    double* dss = sh + PT_BLOCK * E;
+    const int i = threadIdx.x;
+    const int l = blockIdx.x * PT_BLOCK + i;
+    const int nv = min(PT_BLOCK, po.ntc - blockIdx.x * PT_BLOCK);   // the block's particles
+    if (i < nv) {
+        for (int e = 0; e < E; ++e) xs[i * E + e] = po.x[(long)(po.p0 + l) * E + e];
+        for (int k = 0; k < U; ++k) dss[i * U + k] = a.ds[(long)k * a.ldg + l];
+    }
+    if (po.kind == PILCO_POLICY_RBF)
+        for (int q = i; q < U * E; q += PT_BLOCK) il_s[q] = 1.0 / po.pls[q];
+    __syncthreads();
+    double* cell = a.part + (long)(po.p0 / PT_BLOCK + blockIdx.x) * Q;
+    // k_kc of particle j: the basis function as k_particle_head evaluates it
+    auto basis = [&](int j, int k, int c) {
+        double r2 = 0.0;
+        for (int e = 0; e < E; ++e) {
+            const double d = (xs[j * E + e] - po.pc[(long)e * po.pnpad + c]) * il_s[k * E + e];
+            r2 = fma(d, d, r2);
+        }
+        return po.pvar[k] * exp(-0.5 * r2);
+    };
+    for (int q = i; q < Q; q += PT_BLOCK) {
+        double s = 0.0;
+        if (po.kind == PILCO_POLICY_LINEAR) {
+            if (q < U * E) {
+                const int k = q / E, e = q - k * E;
+                for (int j = 0; j < nv; ++j) s = fma(dss[j * U + k], xs[j * E + e], s);
+            } else {
+                const int k = q - U * E;
+                for (int j = 0; j < nv; ++j) s += dss[j * U + k];
+            }
+        } else if (q < U * bf) {                     // d beta_kc = sum ds_k k_kc
+            const int k = q / bf, c = q - k * bf;
+            for (int j = 0; j < nv; ++j) s = fma(dss[j * U + k], basis(j, k, c), s);
+        } else if (q < U * bf + bf * E) {            // d C_ce = sum_k w_kc (x_e - c_ce) / l_ke^2
+            const int ce = q - U * bf, c = ce / E, e = ce - c * E;
+            const double cc = po.pc[(long)e * po.pnpad + c];
+            for (int j = 0; j < nv; ++j)
+                for (int k = 0; k < U; ++k) {
+                    const double w = dss[j * U + k] * po.pbeta[(long)k * po.pnpad + c] * basis(j, k, c);
+                    const double il = il_s[k * E + e];
+                    s = fma(w, (xs[j * E + e] - cc) * (il * il), s);
+                }
+        } else {                                     // d l_ke = sum_c w_kc (x_e - c_ce)^2 / l_ke^3
+            const int ke = q - U * bf - bf * E, k = ke / E, e = ke - k * E;
+            const double il = il_s[ke], il3 = il * il * il;
+            for (int j = 0; j < nv; ++j)
+                for (int c = 0; c < bf; ++c) {
+                    const double w = dss[j * U + k] * po.pbeta[(long)k * po.pnpad + c] * basis(j, k, c);
+                    const double d = xs[j * E + e] - po.pc[(long)e * po.pnpad + c];
+                    s = fma(w, d * d * il3, s);
+                }
+        }
+        cell[q] += s;
+    }
+}
+
+// thread q: the blocks' cells of quantity q in block order, over P.  part [nblk][Q] -> out [Q]
+__global__ __launch_bounds__(PT_BLOCK) void k_pg_finish(const double* part, double* out, int nblk, int Q, int P) {
+    const int q = blockIdx.x * PT_BLOCK + threadIdx.x;
+    if (q >= Q) return;
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += part[(long)b * Q + q];
+    out[q] = s / (double)P;
+}
+
+}  // namespace pilco
+
+using namespace pilco;
+
+namespace {
+
+size_t group_budget() {
+    if (const char* v = getenv("PILCO_PARTICLE_GRAD_BUDGET")) {
+        const long long n = atoll(v);
+        if (n > 0) return (size_t)n;
+    }
+    return PG_BUDGET;
+}
+
+// Both entry points.  par: LinearController dW (U,E) | db (U); RbfController dbeta (U,bf) | dC (bf,E) | dl (U,E), over P.
+int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0,
+                           int P, int H, const double* eps, unsigned long long seed, int observation_noise, double* reward,
+                           double* reward_steps, std::vector<double>& par, double* dreturn_dx0) {
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    const int E = s.E, D = s.D, U = D - E;
+    const int bf = policy->kind == PILCO_POLICY_RBF ? ctx->slot[PILCO_SLOT_POLICY].N : 0;
+    const int Q = U > 0 ? pg_quantities(policy->kind, E, U, bf) : 0;
+    par.assign((size_t)Q, 0.0);
+    const size_t PE = (size_t)P * E;
+    if (H == 0) {
+        *reward = 0.0;
+        if (dreturn_dx0) std::fill(dreturn_dx0, dreturn_dx0 + PE, 0.0);
+        return PILCO_OK;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!s.factor_valid)
+        if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
+    if (!s.pred) s.pred = new PredictWork();
+    PredictWork& pw = *s.pred;
+    hipStream_t st = ctx->st;
+    const PredictModel md = predict_model_of(s, 0, E);
+    const int npad = md.npad;
+    const int nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
+    // the groups: a multiple of PT_BLOCK particles whose matrices fit the budget (at least one block)
+    const size_t per_particle = (size_t)(H - 1) * E * D;
+    int Pg = P;
+    if (per_particle * (size_t)P > group_budget())
+        Pg = (int)std::min<size_t>((size_t)round_up(P, PT_BLOCK), std::max<size_t>(1, group_budget() / per_particle / PT_BLOCK) * PT_BLOCK);
+    const int ldg = round_up(std::min(Pg, P), 64);
+    const int ntc_max = std::min(ldg, predict_chunk_cap(E, npad));
+    std::vector<double> hp(particle_par_doubles(E, U), 0.0);
+    std::vector<double> hout((size_t)H + Q), hlam(dreturn_dx0 ? (size_t)E * ldg : 0);
+    ENSURE(pw.Xt, (size_t)D * ntc_max);
+    ENSURE(pw.Ks, (size_t)E * ntc_max * npad);
+    ENSURE(pw.out, (size_t)2 * E * ntc_max);
+    if (H > 1) {
+        ENSURE(pw.jac, (size_t)2 * E * ntc_max * D);
+        ENSURE(pw.jacW, (size_t)predict_jac_nops(md) * E * ntc_max * npad);
+        ENSURE(pw.pg_A, per_particle * ldg);
+    }
+    ENSURE(pw.pt_x, (size_t)(H + 1) * PE);
+    ENSURE(pw.pt_eps, (size_t)H * PE);
+    ENSURE(pw.pt_rew, (size_t)P);
+    ENSURE(pw.pt_par, hp.size());
+    ENSURE(pw.pg_lam, (size_t)2 * E * ldg);
+    ENSURE(pw.pg_ds, (size_t)std::max(U, 1) * ldg);
+    ENSURE(pw.pg_part, (size_t)nblk * std::max(Q, 1));
+    ENSURE(pw.pg_rew, (size_t)H * nblk);
+    ENSURE(pw.pg_out, hout.size());
+
+    PgReverseArgs ra{};
+    ParticleTailArgs ta{};
+    size_t off = 0;
+    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ra.pol);
+    ta.n_rewards = ra.n_rewards = n_rewards;
+    stage_rewards(rewards, n_rewards, E, hp, off, pw.pt_par.p, ta.rw);
+    for (int i = 0; i < n_rewards; ++i) ra.rw[i] = ta.rw[i];
+    ParticleHeadArgs ha = ra.pol;
+    StreamDrain drain{st};
+    // one upload: parameters, initial particles, the caller's draws
+    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
+    if (eps) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
+    if (Q > 0) HIPCHK(hipMemsetAsync(pw.pg_part.p, 0, sizeof(double) * nblk * Q, st));
+
+    ta.E = E; ta.seed = seed;
+    ta.noise = observation_noise ? s.noise.p : nullptr;
+    ta.rew = pw.pt_rew.p;
+    PgFoldArgs fa{};
+    fa.noise = ta.noise; fa.ldg = ldg; fa.E = E; fa.D = D;
+    PgParamArgs pa{};
+    pa.ds = ra.ds = pw.pg_ds.p; pa.part = pw.pg_part.p; pa.ldg = ra.ldg = ldg; pa.Q = Q;
+    const int lds_bytes = (int)sizeof(double) * pg_reverse_lds_doubles(E, U);
+    auto slab = [&](int t) { return pw.pt_x.p + (size_t)t * PE; };
+    for (int g0 = 0; g0 < P; g0 += Pg) {
+        const int ng = std::min(Pg, P - g0), nbg = (ng + PT_BLOCK - 1) / PT_BLOCK;
+        for (int t = 0; t < H; ++t) {
+            const bool jac = t < H - 1;
+            double* eps_t = pw.pt_eps.p + (size_t)t * PE;
+            ha.x = ta.x = slab(t);
+            ta.xn = slab(t + 1);
+            ta.t = t;
+            ta.eps_in = eps ? eps_t : nullptr;
+            ta.eps_out = eps ? nullptr : eps_t;
+            for (int l0 = 0; l0 < ng; l0 += ntc_max) {
+                const int p0 = g0 + l0, ntc = std::min(ntc_max, ng - l0), ldt = round_up(ntc, 64);
+                double *out_mean = pw.out.p, *out_var = pw.out.p + (size_t)E * ldt;
+                ha.Xt = pw.Xt.p; ha.p0 = p0; ha.ntc = ntc; ha.ldt = ldt;
+                launch_particle_head(st, ha);
+                if (int r = predict_points_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, out_mean, out_var)) return r;
+                ta.mu = out_mean; ta.var = out_var; ta.p0 = p0; ta.ntc = ntc; ta.ldt = ldt;
+                launch_particle_tail(st, ta);
+                if (!jac) continue;
+                double *dm = pw.jac.p, *dv = pw.jac.p + (size_t)E * ldt * D;
+                if (int r = predict_points_jac_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, pw.jacW.p, dm, dv)) return r;
+                fa.dmean = dm; fa.dvar = dv; fa.var = out_var; fa.eps = eps_t;
+                fa.A = pw.pg_A.p + (size_t)t * E * D * ldg;
+                fa.p0 = p0; fa.l0 = l0; fa.ntc = ntc; fa.ldt = ldt;
+                hipLaunchKernelGGL(k_pg_fold, dim3((ntc + 255) / 256, E), dim3(256), 0, st, fa);
+            }
+            hipLaunchKernelGGL(k_pg_reward_partials, dim3((nbg + 63) / 64), dim3(64), 0, st, (const double*)pw.pt_rew.p,
+                               pw.pg_rew.p, P, g0 / PT_BLOCK, nbg, t, H);
+        }
+        ra.pol.p0 = g0; ra.pol.ntc = ng;
+        for (int t = H - 1; t >= 0; --t) {
+            const int in = (H - 1 - t) & 1;
+            ra.pol.x = slab(t);
+            ra.A = t < H - 1 ? pw.pg_A.p + (size_t)t * E * D * ldg : nullptr;
+            ra.lam_in = pw.pg_lam.p + (size_t)in * E * ldg;
+            ra.lam_out = pw.pg_lam.p + (size_t)(in ^ 1) * E * ldg;
+            hipLaunchKernelGGL(k_pg_reverse, dim3((ng + PG_RB - 1) / PG_RB), dim3(PG_RB), lds_bytes, st, ra);
+            if (Q > 0 && t < H - 1) {
+                pa.pol = ra.pol;
+                hipLaunchKernelGGL(k_pg_param_partials, dim3(nbg), dim3(PT_BLOCK), 0, st, pa);
+            }
+        }
+        HIPCHK(hipGetLastError());
+        if (dreturn_dx0) {   // lam_0, [E][ldg]: the group's download and synchronisation
+            const double* lam0 = pw.pg_lam.p + (size_t)(H & 1) * E * ldg;
+            HIPCHK(hipMemcpyAsync(hlam.data(), lam0, sizeof(double) * E * ldg, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (int l = 0; l < ng; ++l)
+                for (int e = 0; e < E; ++e) dreturn_dx0[(size_t)(g0 + l) * E + e] = hlam[(size_t)e * ldg + l];
+        }
+    }
+    // the rewards of the steps as k_particle_finish has them, and the parameter sums: one download, one synchronisation
+    hipLaunchKernelGGL(k_pg_finish, dim3((H + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, (const double*)pw.pg_rew.p, pw.pg_out.p,
+                       nblk, H, P);
+    if (Q > 0)
+        hipLaunchKernelGGL(k_pg_finish, dim3((Q + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, (const double*)pw.pg_part.p,
+                           pw.pg_out.p + H, nblk, Q, P);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hout.data(), pw.pg_out.p, sizeof(double) * hout.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double total = 0.0;
+    for (int t = 0; t < H; ++t) total += hout[t];   // J: the steps' rewards added in step order
+    *reward = total;
+    if (reward_steps) memcpy(reward_steps, hout.data(), sizeof(double) * H);
+    std::copy(hout.begin() + H, hout.end(), par.begin());
+    return PILCO_OK;
+}
+
+// the refusals of both entry points, before any launch or upload
+int check_grad_call(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0, int P,
+                    int H, const double* reward, bool rbf) {
+    if (int r = check_particle_state(ctx, P, H)) return r;
+    if (!x0 || !reward) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad: null x0 or reward");
+    if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
+    if (rbf != (policy->kind == PILCO_POLICY_RBF))
+        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad: no policy or a LinearController (pilco_rollout_particles_grad), an "
+                                        "RbfController (pilco_rollout_particles_grad_rbf)");
+    return PILCO_OK;
+}
+
+}  // namespace
+
+extern "C" int pilco_rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                            const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                            int observation_noise, double* reward, double* reward_steps, double* dW, double* db,
+                                            double* dreturn_dx0) {
+    if (!ctx) return PILCO_E_SHAPE;
+    if (int r = check_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, false)) return r;
+    if (policy->kind == PILCO_POLICY_LINEAR && (!dW || !db)) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad: null dW or db");
+    std::vector<double> par;
+    if (int r = rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
+                                       dreturn_dx0))
+        return r;
+    if (policy->kind == PILCO_POLICY_LINEAR) {
+        const size_t UE = (size_t)policy->control_dim * policy->state_dim;
+        memcpy(dW, par.data(), sizeof(double) * UE);
+        memcpy(db, par.data() + UE, sizeof(double) * policy->control_dim);
+    }
+    return PILCO_OK;
+}
+
+extern "C" int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards,
+                                                int n_rewards, const double* x0, int P, int H, const double* eps,
+                                                unsigned long long seed, int observation_noise, const double* Xp, const double* Yp,
+                                                const double* lsp, const double* noisep, int bf, double* reward, double* reward_steps,
+                                                double* dX, double* dY, double* dls, double* dreturn_dx0) {
+    if (!ctx) return PILCO_E_SHAPE;
+    if (int r = check_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, true)) return r;
+    if (!Xp || !Yp || !lsp || !noisep || !dX || !dY || !dls)
+        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad_rbf: null policy parameters or null dX, dY or dls");
+    if (bf != ctx->slot[PILCO_SLOT_POLICY].N)
+        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad_rbf: bf is not the number of points of the policy slot");
+    const int E = policy->state_dim, U = policy->control_dim;
+    if (!rbf_solve_adjoint(bf, E, U, Xp, Yp, lsp, noisep, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return fail(ctx, PILCO_E_NOT_PD, "rollout_particles_grad_rbf: K + noise I of the policy is singular");
+    std::vector<double> par;
+    if (int r = rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
+                                       dreturn_dx0))
+        return r;
+    // dbeta (U,bf) | dC (bf,E) | dl (U,E): dbeta through beta_k = (K_k + noise_k I)^-1 Y_k into dY, dX and dls
+    const double *dbeta = par.data(), *dC = dbeta + (size_t)U * bf, *dl = dC + (size_t)bf * E;
+    rbf_solve_adjoint(bf, E, U, Xp, Yp, lsp, noisep, dC, dl, dbeta, dX, dY, dls);
+    return PILCO_OK;
+}

@@ -7,12 +7,14 @@ constexpr size_t PP_KS_BUDGET = size_t(1) << 24;   // doubles of cross-covarianc
 
 // the per-call buffers of the predictions, and the FITC operands of per-output inducing inputs (a slot of its own whose
 // data, targets and hyper-parameters are views of the parent slot's); pt_*: the particle rollout's buffers (particles.hip),
-// pt_ev_*: its events' integers (first hits, block counts, counts) in buffers of doubles
+// pt_ev_*: its events' integers (first hits, block counts, counts) in buffers of doubles; pg_*: the buffers of the
+// particle gradient (particles_grad.hip)
 struct PredictWork {
     DevBuf raw, Xt, Ks, out, jac, jacW;
     Slot fitc;
     DevBuf pt_x, pt_eps, pt_rew, pt_part, pt_stats, pt_par;
     DevBuf pt_ev_first, pt_ev_part, pt_ev_counts;
+    DevBuf pg_A, pg_lam, pg_ds, pg_part, pg_rew, pg_out;
 };
 
 // The operator blocks and the points of the cross-covariance of Eu outputs of one model (device pointers).

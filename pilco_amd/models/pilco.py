@@ -166,9 +166,12 @@ class PILCO:
                     float(model.kernel.variance.numpy()), float(model.likelihood.variance.numpy())))
 
     # pilco.py:75-113
-    def optimize_policy(self, maxiter=50, restarts=1, verbose=True):
+    def optimize_policy(self, maxiter=50, restarts=1, verbose=True, objective="moment_matching", particle_options=None):
+        """objective="particles" (extension): maximise the particle return of particle_value_and_gradient on fixed initial
+        particles and draws instead of the moment-matched reward; particle_options: num_particles, seed, observation_noise."""
         from ..training import optimize_policy
-        return optimize_policy(self, maxiter=maxiter, restarts=restarts, verbose=verbose)
+        return optimize_policy(self, maxiter=maxiter, restarts=restarts, verbose=verbose, objective=objective,
+                               particle_options=particle_options)
 
     # pilco.py:115-116
     def value_and_gradient(self, seed_fn=None):
@@ -190,6 +193,49 @@ class PILCO:
         r, dX, dY, dl = self.ctx.rollout_grad_rbf(self._policy_spec(), self._reward_terms(), self.m_init, self.S_init, self.horizon,
                                                   ctl.X, ctl.Y, ctl.lengthscales, ctl.noise, seed_fn=seed_fn)
         return r, (dX, dY, dl)
+
+    def _initial_particles(self, m_x, s_x, num_particles, seed):
+        """x0 = m_x + z sqrt(s_x): z from np.random.default_rng(seed), the symmetric square root, eigenvalues clipped at zero"""
+        E = self.state_dim
+        m = np.asarray(m_x, np.float64).reshape(1, E)
+        w, V = np.linalg.eigh(0.5 * (np.asarray(s_x, np.float64).reshape(E, E) + np.asarray(s_x, np.float64).reshape(E, E).T))
+        root = (V * np.sqrt(np.clip(w, 0.0, None))) @ V.T
+        return m + np.random.default_rng(seed).standard_normal((int(num_particles), E)) @ root
+
+    def particle_value_and_gradient(self, m_x=None, s_x=None, n=None, num_particles=1000, seed=0, eps=None, x0=None,
+                                    observation_noise=False, return_dx0=False):
+        """Extension: (reward, grads) of the PARTICLE return -- sample_trajectories(...).reward_steps.sum() on the same initial
+        particles and draws -- w.r.t. the controller parameters, on the device (pilco_rollout_particles_grad / _grad_rbf;
+        docs/particle_gradients.md).  grads has the structure value_and_gradient returns: (dW, db) for a LinearController,
+        (dX, dY, dlengthscales) for an RbfController, () without a controller.  m_x, s_x, n default to m_init, S_init and
+        horizon; x0, eps, seed and observation_noise are those of sample_trajectories.  With x0 (or seed) and the draws fixed
+        the value is a deterministic, smooth function of the parameters (common random numbers).  return_dx0: a third
+        result (P, E), row p the gradient of particle p's own return w.r.t. its initial state.  Any reward term evaluated on
+        the host raises NotImplementedError, event terms included: an indicator has no gradient."""
+        if self._host_reward_terms():
+            raise NotImplementedError("particle_value_and_gradient: reward terms evaluated on the host (events included) are not "
+                                      "part of the differentiated objective")
+        ctl = self.controller if self.control_dim > 0 else None
+        linear = isinstance(ctl, controllers.LinearController)
+        if ctl is not None and not linear and not isinstance(ctl, controllers.RbfController):
+            raise TypeError("particle policy gradient: LinearController or RbfController")
+        m_x = self.m_init if m_x is None else m_x
+        s_x = self.S_init if s_x is None else s_x
+        n = self.horizon if n is None else int(n)
+        if x0 is None:
+            x0 = self._initial_particles(m_x, s_x, num_particles, seed)
+        x0 = np.asarray(x0, np.float64).reshape(-1, self.state_dim)
+        self.mgpr._user_factors = None
+        self.mgpr._ensure_factorized()
+        kw = dict(eps=eps, seed=seed, observation_noise=observation_noise, want_dx0=return_dx0)
+        if ctl is None or linear:
+            r, _, dW, db, dx0 = self.ctx.rollout_particles_grad(self._policy_spec(), self._reward_terms(), x0, n, **kw)
+            grads = (dW.reshape(ctl.W.shape), db.reshape(ctl.b.shape)) if linear else ()
+        else:
+            r, _, dX, dY, dl, dx0 = self.ctx.rollout_particles_grad_rbf(self._policy_spec(), self._reward_terms(), x0, n,
+                                                                        ctl.X, ctl.Y, ctl.lengthscales, ctl.noise, **kw)
+            grads = (dX, dY, dl)
+        return (r, grads, dx0) if return_dx0 else (r, grads)
 
     def compute_action(self, x_m):
         return self.controller.compute_action(x_m, np.zeros([self.state_dim, self.state_dim]))[0]
@@ -271,10 +317,7 @@ class PILCO:
         table = (list(events) if events is not None else []) + [r for _, r in host]
         E = self.state_dim
         if x0 is None:
-            m = np.asarray(m_x, np.float64).reshape(1, E)
-            w, V = np.linalg.eigh(0.5 * (np.asarray(s_x, np.float64).reshape(E, E) + np.asarray(s_x, np.float64).reshape(E, E).T))
-            root = (V * np.sqrt(np.clip(w, 0.0, None))) @ V.T
-            x0 = m + np.random.default_rng(seed).standard_normal((int(num_particles), E)) @ root
+            x0 = self._initial_particles(m_x, s_x, num_particles, seed)
         x0 = np.asarray(x0, np.float64).reshape(-1, E)
         self.mgpr._user_factors = None
         self.mgpr._ensure_factorized()

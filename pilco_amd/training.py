@@ -595,20 +595,59 @@ def _optimize_policy_lanes(pilco, maxiter, restarts, verbose, seeded=False):
     return best_r
 
 
-def optimize_policy(pilco, maxiter=50, restarts=1, verbose=True):
+def particle_loss_and_grad(pilco, u, put, x0, seed, observation_noise):
+    """-J and its gradient for the particle return on the fixed initial particles x0 and the draws of `seed`
+    (PILCO.particle_value_and_gradient)."""
+    from .controllers import LinearController
+    put(u)
+    r, grads = pilco.particle_value_and_gradient(x0=x0, seed=seed, observation_noise=observation_noise)
+    if isinstance(pilco.controller, LinearController):
+        Wb, bb = grads
+        return -r, -np.concatenate([Wb.ravel(), bb.ravel()])
+    Xb, Yb, lb = grads
+    nu = lb.size                                                 # ls = lower + softplus(u): d ls / du = sigmoid(u)
+    return -r, -np.concatenate([Xb.ravel(), Yb.ravel(), (lb * _dsoftplus(u[-nu:]).reshape(lb.shape)).ravel()])
+
+
+def optimize_policy(pilco, maxiter=50, restarts=1, verbose=True, objective="moment_matching", particle_options=None):
+    """objective="moment_matching" (default): the reference's walk on the moment-matched reward.  objective="particles": the
+    same L-BFGS-B walk on minus the particle return (common random numbers: the initial particles and the seed of the draws
+    are fixed over the whole walk and over the restarts, so the objective is deterministic and smooth); the restarts run one
+    after the other and are compared by their particle return.  particle_options: num_particles (1000), seed (0),
+    observation_noise (False)."""
+    if objective not in ("moment_matching", "particles"):
+        raise ValueError("optimize_policy: objective is 'moment_matching' or 'particles'")
     if pilco.controller is None:
         raise ValueError("optimize_policy: the model has no controller (control_dim == 0)")
-    lanes = _restart_lanes_apply(pilco, restarts) if restarts >= 2 else False
+    particles = objective == "particles"
+    if particles:
+        opts = dict(num_particles=1000, seed=0, observation_noise=False)
+        unknown = set(particle_options or {}) - set(opts)
+        if unknown:
+            raise ValueError("optimize_policy: unknown particle_options %s" % sorted(unknown))
+        opts.update(particle_options or {})
+        seed, obs = int(opts["seed"]), bool(opts["observation_noise"])
+        x0 = pilco._initial_particles(pilco.m_init, pilco.S_init, opts["num_particles"], seed)
+    elif particle_options is not None:
+        raise ValueError("optimize_policy: particle_options go with objective='particles'")
+    lanes = _restart_lanes_apply(pilco, restarts) if (restarts >= 2 and not particles) else False
     if lanes:
         return _optimize_policy_lanes(pilco, maxiter, restarts, verbose, seeded=(lanes == "seeded"))
     get, put = _policy_params(pilco.controller)
 
+    def loss(u):
+        if particles:
+            return particle_loss_and_grad(pilco, u, put, x0, seed, obs)
+        return policy_loss_and_grad(pilco, u, put)
+
     def run():
         start = time.time()
-        res = minimize(lambda u: policy_loss_and_grad(pilco, u, put), get(), jac=True, method="L-BFGS-B",
-                       options=dict(maxiter=maxiter))
+        res = minimize(loss, get(), jac=True, method="L-BFGS-B", options=dict(maxiter=maxiter))
         put(res.x)
-        r = float(pilco.compute_reward()[0, 0])
+        if particles:
+            r = float(pilco.particle_value_and_gradient(x0=x0, seed=seed, observation_noise=obs)[0])
+        else:
+            r = float(pilco.compute_reward()[0, 0])
         if verbose:
             print("Controller's optimization: done in %.1f seconds with reward=%.3f." % (time.time() - start, r))
         return res.x, r
