@@ -148,12 +148,17 @@ def run(iters=5, seed=0, verbose=True, particle_risk=0):
     if particle_risk:
         r = pilco.sample_risk(m_init, S_init, T, num_particles=int(particle_risk), seed=seed)
         out["risk_sample"] = r
+        # ... and on one posterior function sample per particle (docs/particle_functions.md): a trajectory that comes back to a
+        # region meets the same dynamics there
+        rf = pilco.sample_risk(m_init, S_init, T, num_particles=int(particle_risk), seed=seed, dynamics="function")
+        out["risk_sample_function"] = rf
         if verbose:
             with np.printoptions(precision=3, suppress=True):
                 print("[safe cars] risk per step, moment matching:", r.risk_moment_matched)
-                print("[safe cars] risk per step, %d particles:  " % int(particle_risk), r.risk_particles)
-            print("[safe cars] in the junction at least once within %d steps: moment matching %.3g, particles %.3g"
-                  % (T, r.any_hit_moment_matched, r.any_hit_particles))
+                print("[safe cars] risk per step, %d particles, marginal draws:  " % int(particle_risk), r.risk_particles)
+                print("[safe cars] risk per step, %d particles, function samples:" % int(particle_risk), rf.risk_particles)
+            print("[safe cars] in the junction at least once within %d steps: moment matching %.3g, particles %.3g (marginal draws), "
+                  "%.3g (function samples)" % (T, r.any_hit_moment_matched, r.any_hit_particles, rf.any_hit_particles))
     return out
 
 

@@ -248,6 +248,31 @@ int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_policy* policy,
                                      int observation_noise, const double* Xp, const double* Yp, const double* lsp,
                                      const double* noisep, int bf, double* reward, double* reward_steps, double* dX, double* dY,
                                      double* dls, double* dreturn_dx0);
+/* Particle rollout on posterior FUNCTION samples (extension; docs/particle_functions.md).  pilco_rollout_particles moves a
+ * particle by an independent marginal draw per step; here particle p draws ONE dynamics function f_p from the GP posterior
+ * (pathwise conditioning on a random-Fourier-feature prior with L features, exact GP only) and rolls it out
+ * deterministically: with xt = [x, u],
+ *   phi_el(xt) = sqrt(2 var_e / L) cos(omega_el . xt + b_el),   omega_eld = z_eld / lengthscale_ed,  b_el = 2 pi u
+ *   r_pe = y_e - Phi_e(X) w_pe - sqrt(noise_e) xi_pe,   v_pe = iK_e r_pe   (iK: the slot's own (K + noise I)^-1)
+ *   f_pe(xt) = sum_l w_pel phi_el(xt) + sum_i k_e(xt, X_i) v_pei,   x'_e = x_e + f_pe(xt) [+ sqrt(noise_e) eps[t][p][e]]
+ * Every argument before draws means what it means in pilco_rollout_particles_events; eps and eps_out are read and written
+ * only with observation_noise.  draws: L and either all four of omega (E,L,D), phase (E,L), w (P,E,L), xi (P,E,N) or none of
+ * them (generated from seed, csrc/philox_normal.h, domains 1..4; the features are shared by all particles).  draws_out (may
+ * be NULL, each member may be NULL): the draws used and v (P,E,N); feeding them back reproduces every output bitwise.
+ * A particle's trajectory depends on its own x0 row and its own (w_p, xi_p) only: the same bits alone or in any batch.
+ * All particles' v are live at every step: the call holds E Ppad (Lpad + 2 npad) doubles (Ppad, Lpad, npad: P, L, N rounded
+ * up to 64) and is refused above a budget of 2^29 doubles (the environment's PILCO_PARTICLE_FN_BUDGET, in doubles, read at
+ * every call) with the largest P that fits in the message.  Refuses, before any launch or upload and with nothing written,
+ * what pilco_rollout_particles_events refuses, a sparse slot (PILCO_E_STATE), a null draws, L outside 1..4096 and some but
+ * not all of the four draws given (PILCO_E_SHAPE). */
+#define PILCO_MAX_FN_FEATURES 4096
+typedef struct pilco_function_draws { int L; const double *omega, *phase, *w, *xi; } pilco_function_draws;
+typedef struct pilco_function_draws_out { double *omega, *phase, *w, *xi, *v; } pilco_function_draws_out;
+int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                               const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
+                               double* mean, double* cov, double* reward_steps, double* particles, double* eps_out,
+                               const pilco_event* events, int n_events, long long* counts, int* first_hit,
+                               const pilco_function_draws* draws, const pilco_function_draws_out* draws_out);
 
 /* ------------------------------------------------------------------ reverse mode
  * The reference differentiates training_loss with TensorFlow's autodiff (pilco/models/pilco.py:85-90);

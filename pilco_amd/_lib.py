@@ -54,6 +54,14 @@ class Event(C.Structure):
     _fields_ = [("n_clauses", C.c_int), ("complement", C.c_int), ("clause", EventClause * MAX_EVENT_CLAUSES)]
 
 
+class FunctionDraws(C.Structure):
+    _fields_ = [("L", C.c_int), ("omega", _dp), ("phase", _dp), ("w", _dp), ("xi", _dp)]
+
+
+class FunctionDrawsOut(C.Structure):
+    _fields_ = [("omega", _dp), ("phase", _dp), ("w", _dp), ("xi", _dp), ("v", _dp)]
+
+
 def event_spec_of(ev):
     """An event as the dict the binding takes: dict(clauses=[(dim, low, high), ...], complement=bool), a bound of None meaning
     no bound on that side.  ev: such a dict, or an object with event_spec() (pilco_amd.safe's constraints)."""
@@ -102,6 +110,10 @@ SIGNATURES = {
     "pilco_rollout_particles_events": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
                                                  _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp,
                                                  C.POINTER(Event), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "pilco_rollout_particles_fn": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                             _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp,
+                                             C.POINTER(Event), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                             C.POINTER(FunctionDraws), C.POINTER(FunctionDrawsOut)]),
     "pilco_rollout_particles_grad": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
                                                _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout_particles_grad_rbf": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
@@ -508,6 +520,66 @@ class Context:
         self._chk(self.lib.pilco_rollout_particles_events(*args, ev, K, counts.ctypes.data_as(C.POINTER(C.c_longlong)),
                                                           first.ctypes.data_as(C.POINTER(C.c_int))))
         return mean, cov, rew, parts, used, counts, first
+
+    def rollout_particles_fn(self, policy, rewards, x0, H, num_features=512, function_draws=None, eps=None, seed=0,
+                             observation_noise=False, want_particles=False, events=None, want_draws=False):
+        """P trajectories of H steps, each on ONE dynamics function drawn from the GP posterior (pilco_rollout_particles_fn;
+        docs/particle_functions.md): random Fourier features (num_features of them) conditioned on the data pathwise, exact GP
+        only.  function_draws: None -- generated on the device from ``seed`` -- or a dict of omega (E, L, D), phase (E, L),
+        w (P, E, L), xi (P, E, N), which sets L.  eps (H, P, E) is read, and the draws used are returned, only with
+        observation_noise (else the fifth result is None).  Returns (mean, cov, reward_steps, particles or None, eps used or
+        None, counts or None, first_hit or None, draws or None); draws (want_draws): the dict above plus v (P, E, N)."""
+        E = policy["state_dim"]
+        p, k1 = self._policy(policy)
+        r, k2 = self._rewards(rewards, E)
+        x0 = _f64(x0)
+        if x0.ndim != 2 or x0.shape[1] != E:
+            raise ValueError(f"initial particles must be (P, {E})")
+        P, H = x0.shape[0], int(H)
+        noisy = bool(observation_noise)
+        if eps is not None:
+            eps = _f64(eps)
+            if eps.shape != (H, P, E):
+                raise ValueError(f"draws must be ({H}, {P}, {E})")
+        D = E + policy["control_dim"]
+        N = int(self.lib.pilco_gp_num_points(self.h, SLOT_DYNAMICS))
+        d = FunctionDraws()
+        keep = []
+        if function_draws is None:
+            d.L = int(num_features)
+        else:
+            om = _f64(function_draws["omega"])
+            if om.ndim != 3 or om.shape[0] != E or om.shape[2] != D:
+                raise ValueError(f"function_draws['omega'] must be ({E}, L, {D})")
+            L = om.shape[1]
+            ph, w, xi = _f64(function_draws["phase"]), _f64(function_draws["w"]), _f64(function_draws["xi"])
+            if ph.shape != (E, L) or w.shape != (P, E, L) or xi.shape != (P, E, N):
+                raise ValueError(f"function_draws: phase ({E}, {L}), w ({P}, {E}, {L}), xi ({P}, {E}, {N}) expected")
+            keep = [om, ph, w, xi]
+            d.L, d.omega, d.phase, d.w, d.xi = L, _ptr(om), _ptr(ph), _ptr(w), _ptr(xi)
+        L = int(d.L)
+        out, do = None, None
+        if want_draws and 1 <= L <= 4096 and N > 0:
+            out = dict(omega=np.empty((E, L, D)), phase=np.empty((E, L)), w=np.empty((P, E, L)), xi=np.empty((P, E, N)),
+                       v=np.empty((P, E, N)))
+            do = FunctionDrawsOut(*[_ptr(out[k]) for k in ("omega", "phase", "w", "xi", "v")])
+        mean = np.empty((H + 1, E))
+        cov = np.empty((H + 1, E, E))
+        rew = np.empty((max(H, 0),))
+        parts = np.empty((H + 1, P, E)) if want_particles else None
+        used = np.empty((H, P, E)) if noisy else None
+        events = list(events) if events is not None else None
+        K = len(events) if events is not None else 0
+        ev = self._events(events) if events is not None else None
+        counts = np.zeros((H + 1, K), np.int64) if events is not None else None
+        first = np.full((P, K), -1, np.int32) if events is not None else None
+        self._chk(self.lib.pilco_rollout_particles_fn(
+            self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            1 if noisy else 0, _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used), ev, K,
+            counts.ctypes.data_as(C.POINTER(C.c_longlong)) if events is not None else None,
+            first.ctypes.data_as(C.POINTER(C.c_int)) if events is not None else None,
+            C.byref(d), C.byref(do) if do is not None else None))
+        return mean, cov, rew, parts, used, counts, first, out
 
     def _particle_grad_args(self, policy, rewards, x0, H, eps, seed, observation_noise):
         E = policy["state_dim"]

@@ -1,5 +1,6 @@
-// What the particle rollout (particles.hip) shares with its gradient (particles_grad.hip): the arguments of the action and
-// draw kernels, their launches, and the policy / reward checks and staging.  The kernels themselves live in particles.hip.
+// What the particle rollout (particles.hip) shares with its gradient (particles_grad.hip) and with the function-sample
+// rollout (particles_fn.hip): the arguments of the action, draw, statistics and event kernels, their launches, the reward
+// terms at a point, and the policy / reward checks and staging.  The kernels themselves live in particles.hip.
 #pragma once
 #include "predict.h"
 
@@ -35,6 +36,49 @@ struct ParticleTailArgs {
     ParticleReward rw[MAX_REWARD_TERMS];
 };
 
+// the reward terms at zero covariance at the state xr [E]; A: the arguments of a step kernel (E, n_rewards, rw)
+#if defined(__HIPCC__)
+template <class A>
+__device__ __forceinline__ double particle_reward(const A& a, const double* xr) {
+    const int E = a.E;
+    double total = 0.0;
+    for (int k = 0; k < a.n_rewards; ++k) {
+        const ParticleReward& r = a.rw[k];
+        double v = 0.0;
+        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
+            double q = 0.0;
+            for (int i = 0; i < E; ++i) {
+                double row = 0.0;
+                for (int j = 0; j < E; ++j) row = fma(r.W[i * E + j], xr[j] - r.t[j], row);
+                q = fma(xr[i] - r.t[i], row, q);
+            }
+            v = exp(-0.5 * q);
+        } else {
+            for (int i = 0; i < E; ++i) v = fma(r.W[i], xr[i], v);
+        }
+        total = fma(r.coef, v, total);
+    }
+    return total;
+}
+#endif
+
+struct ParticleStatArgs {
+    const double* x;     // [P][E]
+    const double* rew;   // [P], or nullptr (the last states: no reward)
+    double* part;        // [nblk][Q] partial sums, Q = E + E*E + 1
+    double* out;         // [Q] mean | cov | mean reward
+    int P, E, nblk;
+};
+
+struct ParticleEventArgs {
+    const double* x;     // [P][E] the states after t steps
+    int* first_hit;      // [P][K] the first t with a hit, -1 so far; or nullptr
+    int* part;           // [nblk][K] the blocks' counts
+    long long* counts;   // [K] row t of the counts
+    int P, E, K, t, nblk;
+    pilco_event ev[PILCO_MAX_EVENTS];   // the table travels in the kernel arguments (832 bytes)
+};
+
 }  // namespace pilco
 
 struct StreamDrain {   // the staging vectors of a call are locals: nothing of the stream may outlive them
@@ -45,6 +89,10 @@ struct StreamDrain {   // the staging vectors of a call are locals: nothing of t
 // k_particle_head over the chunk a.p0 .. a.p0 + a.ntc - 1 (a.ldt columns), k_particle_tail over its a.ntc particles
 void launch_particle_head(hipStream_t st, const pilco::ParticleHeadArgs& a);
 void launch_particle_tail(hipStream_t st, const pilco::ParticleTailArgs& a);
+// the statistics of one state over all particles (k_particle_partials, k_particle_finish) and its events (k_particle_events,
+// k_particle_events_finish): the launches of pilco_rollout_particles, shared with the function-sample rollout (particles_fn.hip)
+void launch_particle_stats(hipStream_t st, const pilco::ParticleStatArgs& a);
+void launch_particle_events(hipStream_t st, const pilco::ParticleEventArgs& a);
 // what pilco_rollout_particles refuses about the slot, the context, P and H; about the policy and the reward terms (in this
 // order, with its null-pointer refusals between the two)
 int check_particle_state(pilco_ctx* ctx, int P, int H);

@@ -62,28 +62,6 @@ __global__ __launch_bounds__(256) void k_particle_head(ParticleHeadArgs a) {
     }
 }
 
-__device__ __forceinline__ double particle_reward(const ParticleTailArgs& a, const double* xr) {
-    const int E = a.E;
-    double total = 0.0;
-    for (int k = 0; k < a.n_rewards; ++k) {
-        const ParticleReward& r = a.rw[k];
-        double v = 0.0;
-        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
-            double q = 0.0;
-            for (int i = 0; i < E; ++i) {
-                double row = 0.0;
-                for (int j = 0; j < E; ++j) row = fma(r.W[i * E + j], xr[j] - r.t[j], row);
-                q = fma(xr[i] - r.t[i], row, q);
-            }
-            v = exp(-0.5 * q);
-        } else {
-            for (int i = 0; i < E; ++i) v = fma(r.W[i], xr[i], v);
-        }
-        total = fma(r.coef, v, total);
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(256) void k_particle_tail(ParticleTailArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.ntc) return;
@@ -112,14 +90,6 @@ __global__ __launch_bounds__(256) void k_particle_tail(ParticleTailArgs a) {
     }
     a.rew[p] = particle_reward(a, xr);
 }
-
-struct ParticleStatArgs {
-    const double* x;     // [P][E]
-    const double* rew;   // [P], or nullptr (the last states: no reward)
-    double* part;        // [nblk][Q] partial sums, Q = E + E*E + 1
-    double* out;         // [Q] mean | cov | mean reward
-    int P, E, nblk;
-};
 
 // block b: particles PT_BLOCK b .. ; thread q adds quantity q over them in index order
 __global__ __launch_bounds__(PT_BLOCK) void k_particle_partials(ParticleStatArgs a) {
@@ -165,15 +135,6 @@ __global__ __launch_bounds__(PT_BLOCK) void k_particle_finish(ParticleStatArgs a
     }
 }
 
-struct ParticleEventArgs {
-    const double* x;     // [P][E] the states after t steps
-    int* first_hit;      // [P][K] the first t with a hit, -1 so far; or nullptr
-    int* part;           // [nblk][K] the blocks' counts
-    long long* counts;   // [K] row t of the counts
-    int P, E, K, t, nblk;
-    pilco_event ev[PILCO_MAX_EVENTS];   // the table travels in the kernel arguments (832 bytes)
-};
-
 // block b: particles PT_BLOCK b .. , one thread per particle; a wave counts its hits by ballot, thread k adds the two waves
 __global__ __launch_bounds__(PT_BLOCK) void k_particle_events(ParticleEventArgs a) {
     __shared__ int wave_hits[PT_BLOCK / 64][PILCO_MAX_EVENTS];
@@ -213,6 +174,15 @@ void launch_particle_head(hipStream_t st, const ParticleHeadArgs& a) {
 }
 void launch_particle_tail(hipStream_t st, const ParticleTailArgs& a) {
     hipLaunchKernelGGL(k_particle_tail, dim3((a.ntc + 255) / 256), dim3(256), 0, st, a);
+}
+void launch_particle_stats(hipStream_t st, const ParticleStatArgs& a) {
+    const int Q = a.E + a.E * a.E + 1;
+    hipLaunchKernelGGL(k_particle_partials, dim3(a.nblk), dim3(PT_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_particle_finish, dim3((Q + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, a);
+}
+void launch_particle_events(hipStream_t st, const ParticleEventArgs& a) {
+    hipLaunchKernelGGL(k_particle_events, dim3(a.nblk), dim3(PT_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_particle_events_finish, dim3(1), dim3(64), 0, st, a);
 }
 
 // the policy against the dynamics slot (and, RbfController, the policy slot)
@@ -368,8 +338,7 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
         sa.x = slab(t);
         sa.rew = with_reward ? pw.pt_rew.p : nullptr;
         sa.out = pw.pt_stats.p + (size_t)t * Q;
-        hipLaunchKernelGGL(k_particle_partials, dim3(nblk), dim3(PT_BLOCK), 0, st, sa);
-        hipLaunchKernelGGL(k_particle_finish, dim3((Q + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, sa);
+        launch_particle_stats(st, sa);
     };
     ParticleEventArgs ea{};
     if (K > 0) {
@@ -384,8 +353,7 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
         ea.x = slab(t);
         ea.t = t;
         ea.counts = reinterpret_cast<long long*>(pw.pt_ev_counts.p) + (size_t)t * K;
-        hipLaunchKernelGGL(k_particle_events, dim3(nblk), dim3(PT_BLOCK), 0, st, ea);
-        hipLaunchKernelGGL(k_particle_events_finish, dim3(1), dim3(64), 0, st, ea);
+        launch_particle_events(st, ea);
     };
     stats(0, false);
     count_events(0);

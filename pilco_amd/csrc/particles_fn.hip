@@ -1,0 +1,473 @@
+// Particle rollouts on posterior function samples: pilco_rollout_particles_fn.  docs/particle_functions.md.
+// pilco_rollout_particles moves a particle by an independent marginal draw per step; here particle p draws ONE dynamics
+// function f_p from the GP posterior -- pathwise conditioning (Matheron's rule) on a random-Fourier-feature prior, exact GP
+// only -- and rolls it out deterministically.  With xt = [x, u] in R^D, output e, L features, N training points:
+//   phi_el(xt) = A_e cos(omega_el . xt + b_el),  A_e = sqrt(2 var_e / L),  omega_eld = z_eld / lengthscale_ed,  b_el = 2 pi u
+//   r_pe = y_e - Phi_e(X) w_pe - sqrt(noise_e) xi_pe,      v_pe = iK_e r_pe
+//   f_pe(xt) = sum_l w_pel phi_el(xt) + sum_i k_e(xt, X_i) v_pei,      x'_e = x_e + f_pe(xt) [+ sqrt(noise_e) eps[t][p][e]]
+// SET-UP, once per call (particles along the fast axis everywhere, Ppad / Lpad / npad = P / L / N rounded up to 64):
+//   k_fn_features   omega [E][L][D], phase [E][L] from the stream (philox_normal.h, domains 1 and 2) -- or the caller's, uploaded
+//   k_fn_weights    Wt [E][Lpad][Ppad]: generated (domain 3) or the caller's w transposed; zero past L and past P
+//   k_fn_phix       Phi(X) [E][npad][Lpad] over the slot's Xt; zero past N and past L
+//   launch_gemm     R = Phi(X) Wt                      [E][npad][Ppad]   (full K: column p depends on column p of Wt only)
+//   k_fn_resid      R = (Y - R) - sqrt(noise) xi, xi generated in place (domain 4) or the caller's; zero past N and past P
+//   launch_gemm     V = iK R                           [E][npad][Ppad]
+// STEP, once per step:
+//   k_particle_head (particles.hip)  the actions and the transposed block [x, u] of ALL particles (ldt = Ppad)
+//   k_particle_fn_step               f, the update, the optional noise draw, the reward of the pre-step state
+//   the statistics and event launches of pilco_rollout_particles (launch_particle_stats, launch_particle_events)
+// k_particle_fn_step: a workgroup of FN_WAVES = 8 waves owns 64 particles (one per lane) and ONE output e.  The training points, then
+// the features, are walked in tiles of FN_TILE = 64 staged through LDS (points [i][D], frequencies [l][D], phases [l]: every
+// lane of a wave reads the same word, a broadcast); V and Wt are read straight from memory, 64 consecutive particles of one
+// row per wave, each word once.  ORDER OF THE SUMS: wave w takes the indices 8 w .. 8 w + 7 of every tile, tiles in
+// ascending order, indices in ascending order, one fused multiply-add per term into the wave's two sums
+//   sK_w = sum_i exp(-1/2 sum_d ((xt_d - X_id) / l_d)^2) v_i,        sF_w = sum_l w_l cos(b_l + sum_d omega_ld xt_d)
+// (d ascending inside either); then K = (((sK_0 + sK_1) + sK_2) + ..) + sK_7, F likewise, f = fma(A, F, var K).  No cross-covariance
+// goes to memory, no floating-point atomics; nothing of a particle's arithmetic looks at another lane.
+#include "particle_events.h"
+#include "particles.h"
+#include "philox_normal.h"
+
+#include <cstdlib>
+
+namespace pilco {
+
+constexpr int FN_TILE = 64;
+constexpr int FN_WAVES = 8;                  // waves of a step workgroup
+constexpr int FN_SHARE = FN_TILE / FN_WAVES;   // indices of a tile per wave
+constexpr size_t FN_BUDGET = size_t(1) << 29;   // doubles of weights, residuals and V
+
+struct FnSetupArgs {
+    double *om, *ph;          // [E][L][D], [E][L]
+    double* Wt;               // [E][Lpad][Ppad]
+    double* PhiX;             // [E][npad][Lpad]
+    double* R;                // [E][npad][Ppad]
+    double* xi_out;           // [E][npad][Ppad] the noise draws used, or nullptr
+    const double *w_in, *xi_in;   // the caller's [P][E][L], [P][E][N], or nullptr: generated
+    const double *Xt, *Yt;    // slot: [D][npad], [E][npad]
+    const double *ls, *sf2, *noise;   // [E][D], [E], [E]
+    unsigned long long seed;
+    int E, D, N, npad, L, Lpad, P, Ppad;
+};
+
+__global__ __launch_bounds__(256) void k_fn_features(FnSetupArgs a) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= a.E * a.L) return;
+    const int e = idx / a.L, l = idx - e * a.L, D = a.D;
+    for (int j = 0; 2 * j < D; ++j) {
+        double z[2];
+        philox_domain_normal_pair(a.seed, (uint32_t)l, (uint32_t)e, (uint32_t)j, PHILOX_FN_FREQ, &z[0], &z[1]);
+        for (int h = 0; h < 2 && 2 * j + h < D; ++h) a.om[(long)idx * D + 2 * j + h] = z[h] / a.ls[e * D + 2 * j + h];
+    }
+    a.ph[idx] = philox_fn_phase(a.seed, (uint32_t)l, (uint32_t)e);
+}
+
+// grid (Ppad / 256 rounded up, Lpad): thread p of row l writes Wt[e][l][p] of every output
+__global__ __launch_bounds__(256) void k_fn_weights(FnSetupArgs a) {
+    const int p = blockIdx.x * 256 + threadIdx.x, l = blockIdx.y, E = a.E;
+    if (p >= a.Ppad) return;
+    const bool live = p < a.P && l < a.L;
+    for (int j = 0; 2 * j < E; ++j) {
+        double z[2] = {0.0, 0.0};
+        if (live && !a.w_in) philox_domain_normal_pair(a.seed, (uint32_t)p, (uint32_t)l, (uint32_t)j, PHILOX_FN_WEIGHT, &z[0], &z[1]);
+        for (int h = 0; h < 2 && 2 * j + h < E; ++h) {
+            const int e = 2 * j + h;
+            if (live && a.w_in) z[h] = a.w_in[((long)p * E + e) * a.L + l];
+            a.Wt[((long)e * a.Lpad + l) * a.Ppad + p] = z[h];
+        }
+    }
+}
+
+// grid (npad * Lpad / 256, E): Phi(X)[e][i][l] = A_e cos(b_el + sum_d omega_eld X_id)
+__global__ __launch_bounds__(256) void k_fn_phix(FnSetupArgs a) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const int e = blockIdx.y, i = (int)(idx / a.Lpad), l = (int)(idx - (long)i * a.Lpad);
+    if (i >= a.npad) return;
+    double v = 0.0;
+    if (i < a.N && l < a.L) {
+        const double* om = a.om + ((long)e * a.L + l) * a.D;
+        double arg = a.ph[e * a.L + l];
+        for (int d = 0; d < a.D; ++d) arg = fma(om[d], a.Xt[(long)d * a.npad + i], arg);
+        v = sqrt(2.0 * a.sf2[e] / (double)a.L) * cos(arg);
+    }
+    a.PhiX[((long)e * a.npad + i) * a.Lpad + l] = v;
+}
+
+// grid (Ppad / 256 rounded up, npad): thread p of row i: R[e][i][p] = (y_ei - R[e][i][p]) - sqrt(noise_e) xi_pei
+__global__ __launch_bounds__(256) void k_fn_resid(FnSetupArgs a) {
+    const int p = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y, E = a.E;
+    if (p >= a.Ppad) return;
+    const bool live = p < a.P && i < a.N;
+    for (int j = 0; 2 * j < E; ++j) {
+        double z[2] = {0.0, 0.0};
+        if (live && !a.xi_in) philox_domain_normal_pair(a.seed, (uint32_t)p, (uint32_t)i, (uint32_t)j, PHILOX_FN_XI, &z[0], &z[1]);
+        for (int h = 0; h < 2 && 2 * j + h < E; ++h) {
+            const int e = 2 * j + h;
+            const long at = ((long)e * a.npad + i) * a.Ppad + p;
+            if (live && a.xi_in) z[h] = a.xi_in[((long)p * E + e) * a.N + i];
+            a.R[at] = live ? (a.Yt[(long)e * a.npad + i] - a.R[at]) - sqrt(a.noise[e]) * z[h] : 0.0;
+            if (a.xi_out) a.xi_out[at] = z[h];
+        }
+    }
+}
+
+struct ParticleFnArgs {
+    const double* x;        // [P][E] the step's states
+    double* xn;             // [P][E] the next states
+    const double* Xq;       // [D][Ppad] the step's [x, u], transposed (k_particle_head)
+    const double* Xt;       // [D][npad] training points
+    const double *ls, *sf2; // [E][D], [E]
+    const double* noise;    // [E] likelihood variances (observation_noise), or nullptr
+    const double *om, *ph;  // [E][L][D], [E][L]
+    const double* Wt;       // [E][Lpad][Ppad]
+    const double* V;        // [E][npad][Ppad]
+    const double* eps_in;   // [P][E] the step's draws (observation_noise), or nullptr: generated here
+    double* eps_out;        // [P][E] the draws used, or nullptr
+    double* rew;            // [P] reward of the pre-step state
+    unsigned long long seed;
+    int t, P, Ppad, E, D, N, npad, L, Lpad, n_rewards;
+    ParticleReward rw[MAX_REWARD_TERMS];
+};
+
+// grid (Ppad / 64, E), FN_WAVES waves: see the head of this file.  DM: the register build, D <= DM (the arithmetic of a
+// particle is the same in every build: the loops over d run to D)
+template <int DM>
+__global__ __launch_bounds__(64 * FN_WAVES) void k_particle_fn_step(ParticleFnArgs a) {
+    __shared__ double tile[FN_TILE * DM];   // [index][D]: training points, then frequencies
+    __shared__ double tph[FN_TILE];            // phases of the feature tile
+    __shared__ double red[2][FN_WAVES][64];    // the waves' sums [K | F][wave][lane]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int e = blockIdx.y, D = a.D, N = a.N, L = a.L, npad = a.npad, Ppad = a.Ppad;
+    const long p = (long)blockIdx.x * 64 + lane;   // < Ppad
+    double xt[DM], il[DM];
+#pragma unroll
+    for (int d = 0; d < DM; ++d) {
+        xt[d] = d < D ? a.Xq[(long)d * Ppad + p] : 0.0;
+        il[d] = d < D ? 1.0 / a.ls[e * D + d] : 0.0;
+    }
+    double sK = 0.0, sF = 0.0;
+    const double* Ve = a.V + (long)e * npad * Ppad + p;
+    for (int i0 = 0; i0 < N; i0 += FN_TILE) {
+        __syncthreads();
+        for (int q = tid; q < FN_TILE * D; q += 64 * FN_WAVES) {   // (i0 + ii < npad: the slot pads its points with zeros)
+            const int d = q >> 6, ii = q & 63;
+            tile[ii * D + d] = a.Xt[(long)d * npad + i0 + ii];
+        }
+        __syncthreads();
+        const int end = min(FN_SHARE * (w + 1), N - i0);
+#pragma unroll 1
+        for (int k0 = FN_SHARE * w; k0 < end; k0 += 4) {   // (wave-uniform bounds; the loops inside unroll: xt, il, v stay in registers)
+            double v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = Ve[(long)(i0 + k0 + k) * Ppad];   // rows < npad exist (zero past N)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ii = k0 + k;
+                if (ii < end) {
+                    double r2 = 0.0;
+#pragma unroll
+                    for (int d = 0; d < DM; ++d)
+                        if (d < D) {
+                            const double s = (xt[d] - tile[ii * D + d]) * il[d];
+                            r2 = fma(s, s, r2);
+                        }
+                    sK = fma(exp(-0.5 * r2), v[k], sK);
+                }
+            }
+        }
+    }
+    const double* We = a.Wt + (long)e * a.Lpad * Ppad + p;
+    for (int l0 = 0; l0 < L; l0 += FN_TILE) {
+        __syncthreads();
+        for (int q = tid; q < FN_TILE * D; q += 64 * FN_WAVES) {
+            const int ll = q / D, d = q - ll * D;
+            tile[q] = (l0 + ll < L) ? a.om[((long)e * L + l0 + ll) * D + d] : 0.0;
+        }
+        if (tid < FN_TILE) tph[tid] = (l0 + tid < L) ? a.ph[e * L + l0 + tid] : 0.0;
+        __syncthreads();
+        const int end = min(FN_SHARE * (w + 1), L - l0);
+#pragma unroll 1
+        for (int k0 = FN_SHARE * w; k0 < end; k0 += 4) {
+            double v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = We[(long)(l0 + k0 + k) * Ppad];   // rows < Lpad exist (zero past L)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ll = k0 + k;
+                if (ll < end) {
+                    double arg = tph[ll];
+#pragma unroll
+                    for (int d = 0; d < DM; ++d)
+                        if (d < D) arg = fma(tile[ll * D + d], xt[d], arg);
+                    sF = fma(v[k], cos(arg), sF);
+                }
+            }
+        }
+    }
+    red[0][w][lane] = sK;
+    red[1][w][lane] = sF;
+    __syncthreads();
+    if (w != 0 || p >= a.P) return;
+    double K = red[0][0][lane], F = red[1][0][lane];
+#pragma unroll
+    for (int q = 1; q < FN_WAVES; ++q) {   // wave order
+        K += red[0][q][lane];
+        F += red[1][q][lane];
+    }
+    const double sf2 = a.sf2[e];
+    const double f = fma(sqrt(2.0 * sf2 / (double)L), F, sf2 * K);
+    const int E = a.E;
+    const double* xr = a.x + p * E;
+    double xe = xr[e] + f;
+    if (a.noise) {
+        double z;
+        if (a.eps_in) {
+            z = a.eps_in[p * E + e];
+        } else {
+            double z0, z1;
+            philox_normal_pair(a.seed, (uint32_t)a.t, (uint32_t)p, (uint32_t)(e >> 1), &z0, &z1);
+            z = (e & 1) ? z1 : z0;
+        }
+        xe += sqrt(fmax(a.noise[e], 0.0)) * z;
+        if (a.eps_out) a.eps_out[p * E + e] = z;
+    }
+    a.xn[p * E + e] = xe;
+    if (e == 0) a.rew[p] = particle_reward(a, xr);
+}
+
+}  // namespace pilco
+
+using namespace pilco;
+
+namespace {
+
+size_t fn_budget() {
+    if (const char* v = getenv("PILCO_PARTICLE_FN_BUDGET")) {
+        const long long n = atoll(v);
+        if (n > 0) return (size_t)n;
+    }
+    return FN_BUDGET;
+}
+
+void launch_fn_step(hipStream_t st, const ParticleFnArgs& a) {
+    const dim3 grid(a.Ppad / 64, a.E), block(64 * FN_WAVES);
+    if (a.D <= 4) hipLaunchKernelGGL(k_particle_fn_step<4>, grid, block, 0, st, a);
+    else if (a.D <= 8) hipLaunchKernelGGL(k_particle_fn_step<8>, grid, block, 0, st, a);
+    else if (a.D <= 12) hipLaunchKernelGGL(k_particle_fn_step<12>, grid, block, 0, st, a);
+    else if (a.D <= 16) hipLaunchKernelGGL(k_particle_fn_step<16>, grid, block, 0, st, a);
+    else if (a.D <= 24) hipLaunchKernelGGL(k_particle_fn_step<24>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_particle_fn_step<MAX_D>, grid, block, 0, st, a);
+}
+
+// [E][rows_pad][Ppad] on the device's side -> the caller's [P][E][rows]
+void fn_untranspose(const std::vector<double>& dev, double* out, int E, int rows, int rows_pad, int P, int Ppad) {
+    for (int p = 0; p < P; ++p)
+        for (int e = 0; e < E; ++e)
+            for (int i = 0; i < rows; ++i) out[((size_t)p * E + e) * rows + i] = dev[((size_t)e * rows_pad + i) * Ppad + p];
+}
+
+}  // namespace
+
+extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                          const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                          int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
+                                          double* eps_out, const pilco_event* events, int n_events, long long* counts,
+                                          int* first_hit, const pilco_function_draws* draws, const pilco_function_draws_out* draws_out) {
+    if (int r = check_particle_state(ctx, P, H)) return r;
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    if (!x0 || !mean || !cov) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: null x0, mean or cov");
+    if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
+    const int E = s.E, D = s.D, U = D - E;
+    if (const char* why = event_table_refusal(events, n_events, counts, E))
+        return fail(ctx, PILCO_E_SHAPE, std::string("rollout_particles_fn: ") + why);
+    if (s.M > 0)
+        return fail(ctx, PILCO_E_STATE, "rollout_particles_fn: the slot is sparse (FITC, M > 0); function samples need an exact GP");
+    if (!draws) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: null draws");
+    const int L = draws->L;
+    if (L < 1 || L > PILCO_MAX_FN_FEATURES) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: L must be in 1..4096");
+    const int given = (draws->omega != nullptr) + (draws->phase != nullptr) + (draws->w != nullptr) + (draws->xi != nullptr);
+    if (given != 0 && given != 4)
+        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: omega, phase, w and xi are given together or not at all");
+    const bool own = given == 4;
+    const int N = s.N, npad = s.Npad, Lpad = round_up(L, 64), Ppad = round_up(P, 64);
+    {
+        const size_t per_p = (size_t)E * ((size_t)Lpad + 2 * (size_t)npad), budget = fn_budget();
+        if (per_p * Ppad > budget) {
+            const long long fit = (long long)(budget / per_p / 64 * 64);
+            return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: E Ppad (Lpad + 2 npad) = " + std::to_string(per_p * Ppad) +
+                                                " doubles exceed the budget of " + std::to_string(budget) +
+                                                " (PILCO_PARTICLE_FN_BUDGET); the largest P that fits is " + std::to_string(fit));
+        }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!s.factor_valid)
+        if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
+    if (!s.pred) s.pred = new PredictWork();
+    PredictWork& pw = *s.pred;
+    hipStream_t st = ctx->st;
+    const bool noisy = observation_noise != 0;
+    const size_t PE = (size_t)P * E;
+    const int Q = E + E * E + 1, nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
+    const int nslab = particles ? H + 1 : 2;
+    const bool keep_eps = noisy && H > 0 && (eps || eps_out);
+    const bool want_xi = draws_out && draws_out->xi && !own;
+    const size_t n_om = (size_t)E * L * D, n_ph = (size_t)E * L, n_w = (size_t)P * E * L, n_xi = (size_t)P * E * N;
+    const size_t n_Wt = (size_t)E * Lpad * Ppad, n_V = (size_t)E * npad * Ppad;
+    std::vector<double> hp(particle_par_doubles(E, U), 0.0);
+    std::vector<double> hstats((size_t)(H + 1) * Q);
+    ENSURE(pw.Xt, (size_t)D * Ppad);
+    ENSURE(pw.pt_x, (size_t)nslab * PE);
+    if (keep_eps) ENSURE(pw.pt_eps, (size_t)H * PE);
+    ENSURE(pw.pt_rew, (size_t)P);
+    ENSURE(pw.pt_part, (size_t)nblk * Q);
+    ENSURE(pw.pt_stats, hstats.size());
+    ENSURE(pw.pt_par, hp.size());
+    ENSURE(pw.fn_om, n_om);
+    ENSURE(pw.fn_ph, n_ph);
+    ENSURE(pw.fn_Wt, n_Wt);
+    ENSURE(pw.fn_phix, (size_t)E * npad * Lpad);
+    ENSURE(pw.fn_R, n_V);
+    ENSURE(pw.fn_V, n_V);
+    if (want_xi) ENSURE(pw.fn_xi, n_V);
+    if (own) ENSURE(pw.fn_raw, n_w + n_xi);
+    const int K = n_events;
+    const size_t fh_bytes = sizeof(int) * (size_t)P * K;
+    if (K > 0) {
+        if (first_hit) ENSURE(pw.pt_ev_first, (fh_bytes + 7) / 8);
+        ENSURE(pw.pt_ev_part, (sizeof(int) * (size_t)nblk * K + 7) / 8);
+        ENSURE(pw.pt_ev_counts, (size_t)(H + 1) * K);
+    }
+
+    ParticleHeadArgs ha{};
+    ParticleFnArgs fa{};
+    size_t off = 0;
+    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ha);
+    fa.n_rewards = n_rewards;
+    stage_rewards(rewards, n_rewards, E, hp, off, pw.pt_par.p, fa.rw);
+    StreamDrain drain{st};
+    // one upload: parameters, initial particles, the caller's draws
+    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
+    if (keep_eps && eps) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
+    if (own) {
+        HIPCHK(hipMemcpyAsync(pw.fn_om.p, draws->omega, sizeof(double) * n_om, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(pw.fn_ph.p, draws->phase, sizeof(double) * n_ph, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(pw.fn_raw.p, draws->w, sizeof(double) * n_w, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(pw.fn_raw.p + n_w, draws->xi, sizeof(double) * n_xi, hipMemcpyHostToDevice, st));
+    }
+
+    // set-up: features, weights, residuals, V
+    FnSetupArgs ua{};
+    ua.om = pw.fn_om.p; ua.ph = pw.fn_ph.p; ua.Wt = pw.fn_Wt.p; ua.PhiX = pw.fn_phix.p; ua.R = pw.fn_R.p;
+    ua.xi_out = want_xi ? pw.fn_xi.p : nullptr;
+    ua.w_in = own ? pw.fn_raw.p : nullptr;
+    ua.xi_in = own ? pw.fn_raw.p + n_w : nullptr;
+    ua.Xt = s.Xt.p; ua.Yt = s.Yt.p; ua.ls = s.ls.p; ua.sf2 = s.var.p; ua.noise = s.noise.p;
+    ua.seed = seed; ua.E = E; ua.D = D; ua.N = N; ua.npad = npad; ua.L = L; ua.Lpad = Lpad; ua.P = P; ua.Ppad = Ppad;
+    if (!own) hipLaunchKernelGGL(k_fn_features, dim3((E * L + 255) / 256), dim3(256), 0, st, ua);
+    hipLaunchKernelGGL(k_fn_weights, dim3((Ppad + 255) / 256, Lpad), dim3(256), 0, st, ua);
+    hipLaunchKernelGGL(k_fn_phix, dim3((unsigned)(((long)npad * Lpad + 255) / 256), E), dim3(256), 0, st, ua);
+    GemmDesc g{};
+    g.alpha = 1.0; g.beta = 0.0;
+    g.A = pw.fn_phix.p; g.lda = Lpad; g.sA = (long)npad * Lpad;
+    g.B = pw.fn_Wt.p; g.ldb = Ppad; g.sB = (long)Lpad * Ppad;
+    g.C = pw.fn_R.p; g.ldc = Ppad; g.sC = (long)npad * Ppad;
+    g.M = npad; g.N = Ppad; g.K = Lpad;
+    launch_gemm(st, g, false, false, E);
+    hipLaunchKernelGGL(k_fn_resid, dim3((Ppad + 255) / 256, npad), dim3(256), 0, st, ua);
+    g.A = s.iK.p; g.lda = npad; g.sA = (long)npad * npad;
+    g.B = pw.fn_R.p; g.ldb = Ppad; g.sB = (long)npad * Ppad;
+    g.C = pw.fn_V.p;
+    g.K = npad;
+    launch_gemm(st, g, false, false, E);
+
+    fa.E = E; fa.D = D; fa.N = N; fa.npad = npad; fa.L = L; fa.Lpad = Lpad; fa.P = P; fa.Ppad = Ppad; fa.seed = seed;
+    fa.Xq = pw.Xt.p; fa.Xt = s.Xt.p; fa.ls = s.ls.p; fa.sf2 = s.var.p;
+    fa.noise = noisy ? s.noise.p : nullptr;
+    fa.om = pw.fn_om.p; fa.ph = pw.fn_ph.p; fa.Wt = pw.fn_Wt.p; fa.V = pw.fn_V.p;
+    fa.rew = pw.pt_rew.p;
+    ParticleStatArgs sa{};
+    sa.P = P; sa.E = E; sa.nblk = nblk; sa.part = pw.pt_part.p;
+    auto slab = [&](int t) { return pw.pt_x.p + (size_t)(particles ? t : (t & 1)) * PE; };
+    auto stats = [&](int t, bool with_reward) {
+        sa.x = slab(t);
+        sa.rew = with_reward ? pw.pt_rew.p : nullptr;
+        sa.out = pw.pt_stats.p + (size_t)t * Q;
+        launch_particle_stats(st, sa);
+    };
+    ParticleEventArgs ea{};
+    if (K > 0) {
+        ea.P = P; ea.E = E; ea.K = K; ea.nblk = nblk;
+        ea.first_hit = first_hit ? reinterpret_cast<int*>(pw.pt_ev_first.p) : nullptr;
+        ea.part = reinterpret_cast<int*>(pw.pt_ev_part.p);
+        for (int k = 0; k < K; ++k) ea.ev[k] = events[k];
+        if (first_hit) HIPCHK(hipMemsetAsync(pw.pt_ev_first.p, 0xFF, fh_bytes, st));   // every entry -1
+    }
+    auto count_events = [&](int t) {
+        if (K == 0) return;
+        ea.x = slab(t);
+        ea.t = t;
+        ea.counts = reinterpret_cast<long long*>(pw.pt_ev_counts.p) + (size_t)t * K;
+        launch_particle_events(st, ea);
+    };
+    stats(0, false);
+    count_events(0);
+    ha.Xt = pw.Xt.p; ha.p0 = 0; ha.ntc = P; ha.ldt = Ppad;
+    for (int t = 0; t < H; ++t) {
+        ha.x = fa.x = slab(t);
+        fa.xn = slab(t + 1);
+        fa.t = t;
+        fa.eps_in = (noisy && eps) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
+        fa.eps_out = (noisy && !eps && eps_out) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
+        launch_particle_head(st, ha);
+        launch_fn_step(st, fa);
+        stats(t + 1, true);
+        count_events(t + 1);
+    }
+    HIPCHK(hipGetLastError());
+    // one download, one synchronisation
+    HIPCHK(hipMemcpyAsync(hstats.data(), pw.pt_stats.p, sizeof(double) * hstats.size(), hipMemcpyDeviceToHost, st));
+    if (particles) HIPCHK(hipMemcpyAsync(particles, pw.pt_x.p, sizeof(double) * (H + 1) * PE, hipMemcpyDeviceToHost, st));
+    if (noisy && eps_out && !eps && H > 0) HIPCHK(hipMemcpyAsync(eps_out, pw.pt_eps.p, sizeof(double) * H * PE, hipMemcpyDeviceToHost, st));
+    if (K > 0) {
+        HIPCHK(hipMemcpyAsync(counts, pw.pt_ev_counts.p, sizeof(long long) * (H + 1) * K, hipMemcpyDeviceToHost, st));
+        if (first_hit) HIPCHK(hipMemcpyAsync(first_hit, pw.pt_ev_first.p, fh_bytes, hipMemcpyDeviceToHost, st));
+    }
+    std::vector<double> h_w, h_xi, h_v;
+    if (draws_out) {
+        if (draws_out->omega) HIPCHK(hipMemcpyAsync(draws_out->omega, pw.fn_om.p, sizeof(double) * n_om, hipMemcpyDeviceToHost, st));
+        if (draws_out->phase) HIPCHK(hipMemcpyAsync(draws_out->phase, pw.fn_ph.p, sizeof(double) * n_ph, hipMemcpyDeviceToHost, st));
+        if (draws_out->w && !own) {
+            h_w.resize(n_Wt);
+            HIPCHK(hipMemcpyAsync(h_w.data(), pw.fn_Wt.p, sizeof(double) * n_Wt, hipMemcpyDeviceToHost, st));
+        }
+        if (want_xi) {
+            h_xi.resize(n_V);
+            HIPCHK(hipMemcpyAsync(h_xi.data(), pw.fn_xi.p, sizeof(double) * n_V, hipMemcpyDeviceToHost, st));
+        }
+        if (draws_out->v) {
+            h_v.resize(n_V);
+            HIPCHK(hipMemcpyAsync(h_v.data(), pw.fn_V.p, sizeof(double) * n_V, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (noisy && eps_out && eps && H > 0) memcpy(eps_out, eps, sizeof(double) * H * PE);
+    if (draws_out) {
+        if (draws_out->w) {
+            if (own) memcpy(draws_out->w, draws->w, sizeof(double) * n_w);
+            else fn_untranspose(h_w, draws_out->w, E, L, Lpad, P, Ppad);
+        }
+        if (draws_out->xi) {
+            if (own) memcpy(draws_out->xi, draws->xi, sizeof(double) * n_xi);
+            else fn_untranspose(h_xi, draws_out->xi, E, N, npad, P, Ppad);
+        }
+        if (draws_out->v) fn_untranspose(h_v, draws_out->v, E, N, npad, P, Ppad);
+    }
+    for (int t = 0; t <= H; ++t) {
+        const double* row = &hstats[(size_t)t * Q];
+        memcpy(mean + (size_t)t * E, row, sizeof(double) * E);
+        memcpy(cov + (size_t)t * E * E, row + E, sizeof(double) * E * E);
+        if (t > 0 && reward_steps) reward_steps[t - 1] = row[Q - 1];
+    }
+    return PILCO_OK;
+}

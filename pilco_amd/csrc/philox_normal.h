@@ -8,6 +8,7 @@
 //   u1 = 1 - ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53  in (0, 1],   u2 = ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53  in [0, 1)
 //   r = sqrt(-2 ln u1),   z_2j = r cos(2 pi u2),   z_2j+1 = r sin(2 pi u2)
 // A draw depends on (seed, t, p, e) only: not on the particle count, not on how the particles are chunked.
+// The counter's fourth word is a domain: 0 above; 1..4 below, the function-sample rollout (particles_fn.hip).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -56,6 +57,36 @@ PILCO_PHILOX_HD inline void philox_normal_pair(unsigned long long seed, uint32_t
     const double r = sqrt(-2.0 * log(u1)), a = 6.283185307179586476925 * u2;
     *z0 = r * cos(a);
     *z1 = r * sin(a);
+}
+
+// The streams of the function-sample rollout (particles_fn.hip, docs/particle_functions.md).  The counter's fourth word
+// selects a domain; domain 0 is the step draws above, whose functions and bits stay as they are.  Key and Box-Muller map as
+// above; a draw depends on (seed, indices) only.
+//   domain 1  {l, e, j, 1}  normals 2j, 2j + 1: z_el,2j, z_el,2j+1 (the frequency of feature l of output e is z / lengthscale)
+//   domain 2  {l, e, 0, 2}  u2: the phase b_el = 2 pi u2
+//   domain 3  {p, l, j, 3}  normals: the weights w_p,2j,l, w_p,2j+1,l of particle p (outputs 2j, 2j + 1, feature l)
+//   domain 4  {p, i, j, 4}  normals: the noise draws xi_p,2j,i, xi_p,2j+1,i (outputs 2j, 2j + 1, training point i)
+enum PhiloxDomain : uint32_t { PHILOX_STEP = 0u, PHILOX_FN_FREQ = 1u, PHILOX_FN_PHASE = 2u, PHILOX_FN_WEIGHT = 3u, PHILOX_FN_XI = 4u };
+
+PILCO_PHILOX_HD inline PhiloxWords philox_domain_words(unsigned long long seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t domain) {
+    return philox4x32_10(c0, c1, c2, domain, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+}
+
+// the two normals of the block {c0, c1, c2, domain}
+PILCO_PHILOX_HD inline void philox_domain_normal_pair(unsigned long long seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t domain,
+                                                      double* z0, double* z1) {
+    double u1, u2;
+    philox_uniforms(philox_domain_words(seed, c0, c1, c2, domain), &u1, &u2);
+    const double r = sqrt(-2.0 * log(u1)), a = 6.283185307179586476925 * u2;
+    *z0 = r * cos(a);
+    *z1 = r * sin(a);
+}
+
+// the phase of feature l of output e, in [0, 2 pi)
+PILCO_PHILOX_HD inline double philox_fn_phase(unsigned long long seed, uint32_t l, uint32_t e) {
+    double u1, u2;
+    philox_uniforms(philox_domain_words(seed, l, e, 0u, PHILOX_FN_PHASE), &u1, &u2);
+    return 6.283185307179586476925 * u2;
 }
 
 }  // namespace pilco

@@ -8,13 +8,14 @@ constexpr size_t PP_KS_BUDGET = size_t(1) << 24;   // doubles of cross-covarianc
 // the per-call buffers of the predictions, and the FITC operands of per-output inducing inputs (a slot of its own whose
 // data, targets and hyper-parameters are views of the parent slot's); pt_*: the particle rollout's buffers (particles.hip),
 // pt_ev_*: its events' integers (first hits, block counts, counts) in buffers of doubles; pg_*: the buffers of the
-// particle gradient (particles_grad.hip)
+// particle gradient (particles_grad.hip); fn_*: the features, weights, residuals and V of the function-sample rollout
 struct PredictWork {
     DevBuf raw, Xt, Ks, out, jac, jacW;
     Slot fitc;
     DevBuf pt_x, pt_eps, pt_rew, pt_part, pt_stats, pt_par;
     DevBuf pt_ev_first, pt_ev_part, pt_ev_counts;
     DevBuf pg_A, pg_lam, pg_ds, pg_part, pg_rew, pg_out;
+    DevBuf fn_om, fn_ph, fn_Wt, fn_phix, fn_R, fn_V, fn_xi, fn_raw;   // the function-sample rollout (particles_fn.hip)
 };
 
 // The operator blocks and the points of the cross-covariance of Eu outputs of one model (device pointers).

@@ -18,10 +18,13 @@ class ParticleTrajectories:
     the initial particles), reward (1, 1) = reward_steps.sum() -- comparable with predict(...)[2] --, reward_steps (n,),
     particles (n+1, P, E) or None, eps (n, P, E): the standard-normal draws used.  With events: event_counts (n+1, K), the
     number of particles that hit event k at state t; event_prob = event_counts / P; first_hit (P, K), the first such t of
-    every particle or -1.  None without events."""
+    every particle or -1.  None without events.  function_draws: with dynamics="function" and return_particles=True the
+    dict of omega (E, L, D), phase (E, L), w (P, E, L), xi (P, E, N), v (P, E, N) the call used (docs/particle_functions.md);
+    else None."""
 
-    def __init__(self, mean, cov, reward_steps, particles, eps, event_counts=None, first_hit=None):
+    def __init__(self, mean, cov, reward_steps, particles, eps, event_counts=None, first_hit=None, function_draws=None):
         self.mean, self.cov, self.reward_steps, self.particles, self.eps = mean, cov, reward_steps, particles, eps
+        self.function_draws = function_draws
         self.reward = np.asarray(reward_steps, np.float64).sum().reshape(1, 1)
         self.event_counts, self.first_hit = event_counts, first_hit
         self.event_prob = None if event_counts is None else event_counts / float(first_hit.shape[0])
@@ -296,7 +299,7 @@ class PILCO:
         return M, S, R, traj
 
     def sample_trajectories(self, m_x, s_x, n, num_particles=1000, seed=0, eps=None, x0=None, observation_noise=False,
-                            return_particles=False, events=None):
+                            return_particles=False, events=None, dynamics="marginal", num_features=512, function_draws=None):
         """Extension: num_particles trajectories of n steps sampled through the learned dynamics on the device
         (pilco_rollout_particles), to hold against the Gaussians predict() propagates.  Every particle acts with
         compute_action(x) and moves by a draw from the GP posterior at [x, u] (latent variance; observation_noise adds the
@@ -308,7 +311,18 @@ class PILCO:
         dict(clauses=[(dim, low, high), ...], complement=bool) -- which fill event_counts, event_prob and first_hit of the
         result.  A host reward term that offers event_spec() adds c * counts[t] / P to reward_steps[t], the mean over the
         particles of c * 1[hit]: the term at zero covariance.  Such terms are counted with the caller's events, at most 8
-        together.  Any other host reward term raises NotImplementedError.  Returns a ParticleTrajectories."""
+        together.  Any other host reward term raises NotImplementedError.  Returns a ParticleTrajectories.
+        dynamics="marginal": every step is an independent draw from the posterior marginal at [x, u] (above).
+        dynamics="function": every particle draws ONE dynamics function from the GP posterior -- num_features random Fourier
+        features conditioned on the data pathwise, or the caller's function_draws (the result's function_draws fed back
+        reproduces every output bitwise) -- and follows it deterministically (pilco_rollout_particles_fn,
+        docs/particle_functions.md); eps is then used only with observation_noise (the result's eps is None without it).
+        Exact GP only: an SMGPR raises NotImplementedError.  Any other value raises ValueError."""
+        if dynamics not in ("marginal", "function"):
+            raise ValueError("sample_trajectories: dynamics must be 'marginal' or 'function', got %r" % (dynamics,))
+        if dynamics == "function" and isinstance(self.mgpr, SMGPR):
+            raise NotImplementedError("sample_trajectories: dynamics='function' needs an exact GP (MGPR); function samples of a "
+                                      "sparse model are not supported")
         host = self._host_reward_terms()
         if any(not hasattr(r, "event_spec") for _, r in host):
             raise NotImplementedError("sample_trajectories: reward terms evaluated on the host are not supported on particles; "
@@ -321,6 +335,9 @@ class PILCO:
         x0 = np.asarray(x0, np.float64).reshape(-1, E)
         self.mgpr._user_factors = None
         self.mgpr._ensure_factorized()
+        if dynamics == "function":
+            return self._sample_function_trajectories(x0, int(n), eps, seed, observation_noise, return_particles, events, K, table,
+                                                      host, num_features, function_draws)
         out = self.ctx.rollout_particles(self._policy_spec(), self._reward_terms(), x0, int(n), eps=eps, seed=seed,
                                          observation_noise=observation_noise, want_particles=return_particles,
                                          events=table if (events is not None or host) else None)
@@ -333,6 +350,25 @@ class PILCO:
         if events is None:
             return ParticleTrajectories(mean, cov, rew, parts, used)
         return ParticleTrajectories(mean, cov, rew, parts, used, np.ascontiguousarray(out[5][:, :K]), np.ascontiguousarray(out[6][:, :K]))
+
+    def _sample_function_trajectories(self, x0, n, eps, seed, observation_noise, return_particles, events, K, table, host,
+                                      num_features, function_draws):
+        """sample_trajectories(dynamics="function") behind its checks: x0 (P, E) and the event table are ready."""
+        if function_draws is not None:
+            function_draws = {k: function_draws[k] for k in ("omega", "phase", "w", "xi")}
+        mean, cov, rew, parts, used, counts, first, draws = self.ctx.rollout_particles_fn(
+            self._policy_spec(), self._reward_terms(), x0, n, num_features=num_features, function_draws=function_draws, eps=eps,
+            seed=seed, observation_noise=observation_noise, want_particles=return_particles,
+            events=table if (events is not None or host) else None, want_draws=return_particles)
+        if host:   # the mean over the particles of c * 1[hit] at the pre-step states
+            P = x0.shape[0]
+            for j, (c, _) in enumerate(host):
+                for t in range(n):
+                    rew[t] += c * float(counts[t, K + j]) / P
+        if events is None:
+            return ParticleTrajectories(mean, cov, rew, parts, used, function_draws=draws)
+        return ParticleTrajectories(mean, cov, rew, parts, used, np.ascontiguousarray(counts[:, :K]),
+                                    np.ascontiguousarray(first[:, :K]), function_draws=draws)
 
     # pilco.py:138-153
     def propagate(self, m_x, s_x):
