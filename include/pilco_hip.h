@@ -273,6 +273,38 @@ int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* policy, const
                                double* mean, double* cov, double* reward_steps, double* particles, double* eps_out,
                                const pilco_event* events, int n_events, long long* counts, int* first_hit,
                                const pilco_function_draws* draws, const pilco_function_draws_out* draws_out);
+/* Value and pathwise gradient of the FUNCTION-sample particle return (extension; docs/particle_fn_gradients.md).  With x0,
+ * the draws and (observation_noise) eps fixed, particle p follows one function f_p, and J = sum_t (1/P) sum_p r(x_t^p) over the
+ * pre-step states t = 0..H-1 is a plain deterministic function of the controller parameters: the step matrix is
+ *   A_t[e][d] = [e == d] + d f_pe / d z_d,   z = [x, u],
+ *   d f_pe / d z_d = -sqrt(2 var_e / L) sum_l w_pel sin(omega_el . z + b_el) omega_eld - var_e sum_i k_i v_pei (z_d - X_id) / l_ed^2
+ * (no clamp, no variance derivative; additive observation noise does not enter it), and the reverse sweep, the policy
+ * adjoints, the rewards' gradients and the parameter sums are those of pilco_rollout_particles_grad.  draws / draws_out: as
+ * pilco_rollout_particles_fn (draws_out returns the draws used, so a repeat or a finite-difference call sees the same
+ * functions); eps (H,P,E) is read only with observation_noise (NULL: the stream of seed).  reward = J, the sum in step order of
+ * reward_steps (H, may be NULL), which has the bits of pilco_rollout_particles_fn on the same inputs and draws.  dW, db,
+ * dreturn_dx0: as pilco_rollout_particles_grad.  H = 0: value 0, zero gradients; H = 1: zero policy gradients, dreturn_dx0 =
+ * grad r(x0).
+ * The set-up of pilco_rollout_particles_fn runs once per call and its budget (PILCO_PARTICLE_FN_BUDGET) refuses as there; the
+ * stored matrices, (H-1) P E D doubles, obey PILCO_PARTICLE_GRAD_BUDGET: above it the particles run in groups of a multiple of
+ * 128, each forward then reverse over its own columns of the weights.  Every sum has a fixed order without floating-point
+ * atomics: neither the groups nor the batch change a bit of any output.  One upload; one download and synchronisation per
+ * group (only with dreturn_dx0) and one at the end.  Refuses what pilco_rollout_particles_grad refuses and what
+ * pilco_rollout_particles_fn refuses about the slot, the draws and the budget -- all before any launch or upload, the outputs
+ * untouched. */
+int pilco_rollout_particles_fn_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                    const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                    int observation_noise, const pilco_function_draws* draws,
+                                    const pilco_function_draws_out* draws_out, double* reward, double* reward_steps, double* dW,
+                                    double* db, double* dreturn_dx0);
+/* The same for an RbfController whose GP lives in PILCO_SLOT_POLICY; the arguments after draws_out and the further refusals
+ * are those of pilco_rollout_particles_grad_rbf. */
+int pilco_rollout_particles_fn_grad_rbf(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                        const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                        int observation_noise, const pilco_function_draws* draws,
+                                        const pilco_function_draws_out* draws_out, const double* Xp, const double* Yp,
+                                        const double* lsp, const double* noisep, int bf, double* reward, double* reward_steps,
+                                        double* dX, double* dY, double* dls, double* dreturn_dx0);
 
 /* ------------------------------------------------------------------ reverse mode
  * The reference differentiates training_loss with TensorFlow's autodiff (pilco/models/pilco.py:85-90);

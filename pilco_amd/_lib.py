@@ -119,6 +119,13 @@ SIGNATURES = {
     "pilco_rollout_particles_grad_rbf": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
                                                    _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
                                                    _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles_fn_grad": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                                  _dp, C.c_ulonglong, C.c_int, C.POINTER(FunctionDraws), C.POINTER(FunctionDrawsOut),
+                                                  _dp, _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles_fn_grad_rbf": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int,
+                                                      C.c_int, _dp, C.c_ulonglong, C.c_int, C.POINTER(FunctionDraws),
+                                                      C.POINTER(FunctionDrawsOut), _dp, _dp, _dp, _dp, C.c_int,
+                                                      _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_gp_predict_vjp": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout_tape": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                      _dp, _dp, _dp, _dp, _dp]),
@@ -521,26 +528,10 @@ class Context:
                                                           first.ctypes.data_as(C.POINTER(C.c_int))))
         return mean, cov, rew, parts, used, counts, first
 
-    def rollout_particles_fn(self, policy, rewards, x0, H, num_features=512, function_draws=None, eps=None, seed=0,
-                             observation_noise=False, want_particles=False, events=None, want_draws=False):
-        """P trajectories of H steps, each on ONE dynamics function drawn from the GP posterior (pilco_rollout_particles_fn;
-        docs/particle_functions.md): random Fourier features (num_features of them) conditioned on the data pathwise, exact GP
-        only.  function_draws: None -- generated on the device from ``seed`` -- or a dict of omega (E, L, D), phase (E, L),
-        w (P, E, L), xi (P, E, N), which sets L.  eps (H, P, E) is read, and the draws used are returned, only with
-        observation_noise (else the fifth result is None).  Returns (mean, cov, reward_steps, particles or None, eps used or
-        None, counts or None, first_hit or None, draws or None); draws (want_draws): the dict above plus v (P, E, N)."""
+    def _function_draws(self, policy, P, num_features, function_draws, want_draws):
+        """function_draws (None: num_features of them, generated) -> the pilco_function_draws of a call, its
+        pilco_function_draws_out or None, the dict that receives the draws used or None, and the arrays to keep alive."""
         E = policy["state_dim"]
-        p, k1 = self._policy(policy)
-        r, k2 = self._rewards(rewards, E)
-        x0 = _f64(x0)
-        if x0.ndim != 2 or x0.shape[1] != E:
-            raise ValueError(f"initial particles must be (P, {E})")
-        P, H = x0.shape[0], int(H)
-        noisy = bool(observation_noise)
-        if eps is not None:
-            eps = _f64(eps)
-            if eps.shape != (H, P, E):
-                raise ValueError(f"draws must be ({H}, {P}, {E})")
         D = E + policy["control_dim"]
         N = int(self.lib.pilco_gp_num_points(self.h, SLOT_DYNAMICS))
         d = FunctionDraws()
@@ -563,6 +554,29 @@ class Context:
             out = dict(omega=np.empty((E, L, D)), phase=np.empty((E, L)), w=np.empty((P, E, L)), xi=np.empty((P, E, N)),
                        v=np.empty((P, E, N)))
             do = FunctionDrawsOut(*[_ptr(out[k]) for k in ("omega", "phase", "w", "xi", "v")])
+        return d, do, out, keep
+
+    def rollout_particles_fn(self, policy, rewards, x0, H, num_features=512, function_draws=None, eps=None, seed=0,
+                             observation_noise=False, want_particles=False, events=None, want_draws=False):
+        """P trajectories of H steps, each on ONE dynamics function drawn from the GP posterior (pilco_rollout_particles_fn;
+        docs/particle_functions.md): random Fourier features (num_features of them) conditioned on the data pathwise, exact GP
+        only.  function_draws: None -- generated on the device from ``seed`` -- or a dict of omega (E, L, D), phase (E, L),
+        w (P, E, L), xi (P, E, N), which sets L.  eps (H, P, E) is read, and the draws used are returned, only with
+        observation_noise (else the fifth result is None).  Returns (mean, cov, reward_steps, particles or None, eps used or
+        None, counts or None, first_hit or None, draws or None); draws (want_draws): the dict above plus v (P, E, N)."""
+        E = policy["state_dim"]
+        p, k1 = self._policy(policy)
+        r, k2 = self._rewards(rewards, E)
+        x0 = _f64(x0)
+        if x0.ndim != 2 or x0.shape[1] != E:
+            raise ValueError(f"initial particles must be (P, {E})")
+        P, H = x0.shape[0], int(H)
+        noisy = bool(observation_noise)
+        if eps is not None:
+            eps = _f64(eps)
+            if eps.shape != (H, P, E):
+                raise ValueError(f"draws must be ({H}, {P}, {E})")
+        d, do, out, keep = self._function_draws(policy, P, num_features, function_draws, want_draws)
         mean = np.empty((H + 1, E))
         cov = np.empty((H + 1, E, E))
         rew = np.empty((max(H, 0),))
@@ -623,6 +637,39 @@ class Context:
         self._chk(self.lib.pilco_rollout_particles_grad_rbf(*head, _ptr(Xp), _ptr(Yp), _ptr(lsp), _ptr(noisep), bf, _ptr(rew),
                                                             _ptr(steps), _ptr(dX), _ptr(dY), _ptr(dls), _ptr(dx0)))
         return float(rew[0]), steps, dX, dY, dls, dx0
+
+    def rollout_particles_fn_grad(self, policy, rewards, x0, H, num_features=512, function_draws=None, eps=None, seed=0,
+                                  observation_noise=False, want_dx0=False, want_draws=False):
+        """Value and pathwise gradient of the FUNCTION-sample particle return J = reward_steps.sum() of rollout_particles_fn on
+        the same x0 and draws (pilco_rollout_particles_fn_grad; docs/particle_fn_gradients.md), for no policy or a
+        LinearController.  function_draws, num_features, eps, seed: as rollout_particles_fn.  Returns (reward, reward_steps
+        (H,), dW (U, E), db (U,), dreturn_dx0 (P, E) or None, draws or None); draws (want_draws): the dict rollout_particles_fn
+        returns -- fed back as function_draws it reproduces every output bitwise."""
+        E, U = policy["state_dim"], policy["control_dim"]
+        head, keep, P, H = self._particle_grad_args(policy, rewards, x0, H, eps, seed, observation_noise)
+        d, do, out, keep2 = self._function_draws(policy, P, num_features, function_draws, want_draws)
+        rew = np.zeros((1,)); steps = np.empty((max(H, 0),)); dW = np.zeros((U, E)); db = np.zeros((U,))
+        dx0 = np.empty((P, E)) if want_dx0 else None
+        self._chk(self.lib.pilco_rollout_particles_fn_grad(*head, C.byref(d), C.byref(do) if do is not None else None, _ptr(rew),
+                                                           _ptr(steps), _ptr(dW), _ptr(db), _ptr(dx0)))
+        return float(rew[0]), steps, dW, db, dx0, out
+
+    def rollout_particles_fn_grad_rbf(self, policy, rewards, x0, H, Xp, Yp, lsp, noisep, num_features=512, function_draws=None,
+                                      eps=None, seed=0, observation_noise=False, want_dx0=False, want_draws=False):
+        """The same for an RbfController (pilco_rollout_particles_fn_grad_rbf): (reward, reward_steps, dX (bf, E), dY (bf, U),
+        dls (U, E), dreturn_dx0 or None, draws or None)."""
+        E, U = policy["state_dim"], policy["control_dim"]
+        head, keep, P, H = self._particle_grad_args(policy, rewards, x0, H, eps, seed, observation_noise)
+        d, do, out, keep2 = self._function_draws(policy, P, num_features, function_draws, want_draws)
+        Xp = _f64(Xp); bf = Xp.shape[0]
+        Xp = _f64(Xp, (bf, E)); Yp = _f64(Yp, (bf, U)); lsp = _f64(lsp, (U, E)); noisep = _f64(noisep, (U,))
+        rew = np.zeros((1,)); steps = np.empty((max(H, 0),))
+        dX = np.empty((bf, E)); dY = np.empty((bf, U)); dls = np.empty((U, E))
+        dx0 = np.empty((P, E)) if want_dx0 else None
+        self._chk(self.lib.pilco_rollout_particles_fn_grad_rbf(*head, C.byref(d), C.byref(do) if do is not None else None, _ptr(Xp),
+                                                               _ptr(Yp), _ptr(lsp), _ptr(noisep), bf, _ptr(rew), _ptr(steps),
+                                                               _ptr(dX), _ptr(dY), _ptr(dls), _ptr(dx0)))
+        return float(rew[0]), steps, dX, dY, dls, dx0, out
 
     def particle_actions(self, policy, x):
         """Test aid: the actions (P, U) the particle rollout acts with at the states x (P, E) (pilco_debug_particle_actions)."""

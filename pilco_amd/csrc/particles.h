@@ -1,6 +1,8 @@
 // What the particle rollout (particles.hip) shares with its gradient (particles_grad.hip) and with the function-sample
 // rollout (particles_fn.hip): the arguments of the action, draw, statistics and event kernels, their launches, the reward
-// terms at a point, and the policy / reward checks and staging.  The kernels themselves live in particles.hip.
+// terms at a point, and the policy / reward checks and staging.  The kernels themselves live in particles.hip.  Below them:
+// the arguments and launches of the gradient's reverse sweep (kernels in particles_grad.hip), which the function-sample
+// gradient (particles_fn_grad.hip) runs on its own step matrices.
 #pragma once
 #include "predict.h"
 
@@ -79,7 +81,48 @@ struct ParticleEventArgs {
     pilco_event ev[PILCO_MAX_EVENTS];   // the table travels in the kernel arguments (832 bytes)
 };
 
+// ---- the reverse sweep of the particle gradient (kernels in particles_grad.hip), shared with the function-sample gradient
+// (particles_fn_grad.hip), which feeds it its own step matrices
+
+constexpr int PG_RB = 64;   // particles (threads) per workgroup of the reverse kernel
+
+struct PgReverseArgs {
+    ParticleHeadArgs pol;   // the policy (x: the states of step t, [P][E]; p0: the group's first particle; ntc: its particles)
+    const double* A;        // [E][D][ldg] the step's matrices, or nullptr: lam_in is zero (t = H - 1)
+    const double* lam_in;   // [E][ldg]
+    double* lam_out;        // [E][ldg]
+    double* ds;             // [U][ldg] cotangents of the sines' arguments
+    int ldg, n_rewards;
+    ParticleReward rw[MAX_REWARD_TERMS];
+};
+
+// dynamic LDS: [3 E + U][PG_RB] the particle's lam, x, lam' and g_u / ds (a column per thread), then 1 / lengthscale [U][E]
+inline int pg_reverse_lds_doubles(int E, int U) { return (3 * E + U) * PG_RB + U * E; }
+
+struct PgParamArgs {
+    ParticleHeadArgs pol;   // as PgReverseArgs
+    const double* ds;       // [U][ldg]
+    double* part;           // [blocks of all particles][Q] the blocks' cells
+    int ldg, Q;
+};
+
+// quantities of a policy: LinearController dW [U][E] | db [U]; RbfController dbeta [U][bf] | dC [bf][E] | dl [U][E]
+inline int pg_quantities(int kind, int E, int U, int bf) { return kind == PILCO_POLICY_RBF ? U * bf + bf * E + U * E : U * E + U; }
+
 }  // namespace pilco
+
+// the launches of the reverse sweep: the reward sums of the blocks b0 .. b0 + nb - 1 at step t (k_pg_reward_partials), one
+// reverse step over the group a.pol.p0 .. + a.pol.ntc - 1 (k_pg_reverse), its parameter sums (k_pg_param_partials), and the
+// blocks' cells in block order over P (k_pg_finish)
+void launch_pg_reward_partials(hipStream_t st, const double* rew, double* part, int P, int b0, int nb, int t, int H);
+void launch_pg_reverse(hipStream_t st, const pilco::PgReverseArgs& a);
+void launch_pg_param_partials(hipStream_t st, const pilco::PgParamArgs& a);
+void launch_pg_finish(hipStream_t st, const double* part, double* out, int nblk, int Q, int P);
+// doubles of stored step matrices per group: PILCO_PARTICLE_GRAD_BUDGET, read at every call, or 2^27
+size_t pg_group_budget();
+// the refusals of the gradient entry points, before any launch or upload; who: the entry point without "pilco_" and "_rbf"
+int check_particle_grad_call(pilco_ctx* ctx, const char* who, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                             const double* x0, int P, int H, const double* reward, bool rbf);
 
 struct StreamDrain {   // the staging vectors of a call are locals: nothing of the stream may outlive them
     hipStream_t st;

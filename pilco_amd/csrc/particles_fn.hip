@@ -25,16 +25,12 @@
 // (d ascending inside either); then K = (((sK_0 + sK_1) + sK_2) + ..) + sK_7, F likewise, f = fma(A, F, var K).  No cross-covariance
 // goes to memory, no floating-point atomics; nothing of a particle's arithmetic looks at another lane.
 #include "particle_events.h"
-#include "particles.h"
-#include "philox_normal.h"
+#include "particles_fn.h"
 
 #include <cstdlib>
 
 namespace pilco {
 
-constexpr int FN_TILE = 64;
-constexpr int FN_WAVES = 8;                  // waves of a step workgroup
-constexpr int FN_SHARE = FN_TILE / FN_WAVES;   // indices of a tile per wave
 constexpr size_t FN_BUDGET = size_t(1) << 29;   // doubles of weights, residuals and V
 
 struct FnSetupArgs {
@@ -111,128 +107,12 @@ __global__ __launch_bounds__(256) void k_fn_resid(FnSetupArgs a) {
     }
 }
 
-struct ParticleFnArgs {
-    const double* x;        // [P][E] the step's states
-    double* xn;             // [P][E] the next states
-    const double* Xq;       // [D][Ppad] the step's [x, u], transposed (k_particle_head)
-    const double* Xt;       // [D][npad] training points
-    const double *ls, *sf2; // [E][D], [E]
-    const double* noise;    // [E] likelihood variances (observation_noise), or nullptr
-    const double *om, *ph;  // [E][L][D], [E][L]
-    const double* Wt;       // [E][Lpad][Ppad]
-    const double* V;        // [E][npad][Ppad]
-    const double* eps_in;   // [P][E] the step's draws (observation_noise), or nullptr: generated here
-    double* eps_out;        // [P][E] the draws used, or nullptr
-    double* rew;            // [P] reward of the pre-step state
-    unsigned long long seed;
-    int t, P, Ppad, E, D, N, npad, L, Lpad, n_rewards;
-    ParticleReward rw[MAX_REWARD_TERMS];
-};
-
-// grid (Ppad / 64, E), FN_WAVES waves: see the head of this file.  DM: the register build, D <= DM (the arithmetic of a
-// particle is the same in every build: the loops over d run to D)
+// grid (columns / 64, E), FN_WAVES waves: see the head of this file; the body is fn_step_body (particles_fn.h), shared with
+// k_particle_fn_step_jac.  DM: the register build, D <= DM
 template <int DM>
 __global__ __launch_bounds__(64 * FN_WAVES) void k_particle_fn_step(ParticleFnArgs a) {
-    __shared__ double tile[FN_TILE * DM];   // [index][D]: training points, then frequencies
-    __shared__ double tph[FN_TILE];            // phases of the feature tile
-    __shared__ double red[2][FN_WAVES][64];    // the waves' sums [K | F][wave][lane]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int e = blockIdx.y, D = a.D, N = a.N, L = a.L, npad = a.npad, Ppad = a.Ppad;
-    const long p = (long)blockIdx.x * 64 + lane;   // < Ppad
-    double xt[DM], il[DM];
-#pragma unroll
-    for (int d = 0; d < DM; ++d) {
-        xt[d] = d < D ? a.Xq[(long)d * Ppad + p] : 0.0;
-        il[d] = d < D ? 1.0 / a.ls[e * D + d] : 0.0;
-    }
-    double sK = 0.0, sF = 0.0;
-    const double* Ve = a.V + (long)e * npad * Ppad + p;
-    for (int i0 = 0; i0 < N; i0 += FN_TILE) {
-        __syncthreads();
-        for (int q = tid; q < FN_TILE * D; q += 64 * FN_WAVES) {   // (i0 + ii < npad: the slot pads its points with zeros)
-            const int d = q >> 6, ii = q & 63;
-            tile[ii * D + d] = a.Xt[(long)d * npad + i0 + ii];
-        }
-        __syncthreads();
-        const int end = min(FN_SHARE * (w + 1), N - i0);
-#pragma unroll 1
-        for (int k0 = FN_SHARE * w; k0 < end; k0 += 4) {   // (wave-uniform bounds; the loops inside unroll: xt, il, v stay in registers)
-            double v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = Ve[(long)(i0 + k0 + k) * Ppad];   // rows < npad exist (zero past N)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ii = k0 + k;
-                if (ii < end) {
-                    double r2 = 0.0;
-#pragma unroll
-                    for (int d = 0; d < DM; ++d)
-                        if (d < D) {
-                            const double s = (xt[d] - tile[ii * D + d]) * il[d];
-                            r2 = fma(s, s, r2);
-                        }
-                    sK = fma(exp(-0.5 * r2), v[k], sK);
-                }
-            }
-        }
-    }
-    const double* We = a.Wt + (long)e * a.Lpad * Ppad + p;
-    for (int l0 = 0; l0 < L; l0 += FN_TILE) {
-        __syncthreads();
-        for (int q = tid; q < FN_TILE * D; q += 64 * FN_WAVES) {
-            const int ll = q / D, d = q - ll * D;
-            tile[q] = (l0 + ll < L) ? a.om[((long)e * L + l0 + ll) * D + d] : 0.0;
-        }
-        if (tid < FN_TILE) tph[tid] = (l0 + tid < L) ? a.ph[e * L + l0 + tid] : 0.0;
-        __syncthreads();
-        const int end = min(FN_SHARE * (w + 1), L - l0);
-#pragma unroll 1
-        for (int k0 = FN_SHARE * w; k0 < end; k0 += 4) {
-            double v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = We[(long)(l0 + k0 + k) * Ppad];   // rows < Lpad exist (zero past L)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ll = k0 + k;
-                if (ll < end) {
-                    double arg = tph[ll];
-#pragma unroll
-                    for (int d = 0; d < DM; ++d)
-                        if (d < D) arg = fma(tile[ll * D + d], xt[d], arg);
-                    sF = fma(v[k], cos(arg), sF);
-                }
-            }
-        }
-    }
-    red[0][w][lane] = sK;
-    red[1][w][lane] = sF;
-    __syncthreads();
-    if (w != 0 || p >= a.P) return;
-    double K = red[0][0][lane], F = red[1][0][lane];
-#pragma unroll
-    for (int q = 1; q < FN_WAVES; ++q) {   // wave order
-        K += red[0][q][lane];
-        F += red[1][q][lane];
-    }
-    const double sf2 = a.sf2[e];
-    const double f = fma(sqrt(2.0 * sf2 / (double)L), F, sf2 * K);
-    const int E = a.E;
-    const double* xr = a.x + p * E;
-    double xe = xr[e] + f;
-    if (a.noise) {
-        double z;
-        if (a.eps_in) {
-            z = a.eps_in[p * E + e];
-        } else {
-            double z0, z1;
-            philox_normal_pair(a.seed, (uint32_t)a.t, (uint32_t)p, (uint32_t)(e >> 1), &z0, &z1);
-            z = (e & 1) ? z1 : z0;
-        }
-        xe += sqrt(fmax(a.noise[e], 0.0)) * z;
-        if (a.eps_out) a.eps_out[p * E + e] = z;
-    }
-    a.xn[p * E + e] = xe;
-    if (e == 0) a.rew[p] = particle_reward(a, xr);
+    __shared__ FnStepLds<DM, false> sh;
+    fn_step_body<DM, false>(a, ParticleFnJac{}, sh);
 }
 
 }  // namespace pilco
@@ -249,16 +129,6 @@ size_t fn_budget() {
     return FN_BUDGET;
 }
 
-void launch_fn_step(hipStream_t st, const ParticleFnArgs& a) {
-    const dim3 grid(a.Ppad / 64, a.E), block(64 * FN_WAVES);
-    if (a.D <= 4) hipLaunchKernelGGL(k_particle_fn_step<4>, grid, block, 0, st, a);
-    else if (a.D <= 8) hipLaunchKernelGGL(k_particle_fn_step<8>, grid, block, 0, st, a);
-    else if (a.D <= 12) hipLaunchKernelGGL(k_particle_fn_step<12>, grid, block, 0, st, a);
-    else if (a.D <= 16) hipLaunchKernelGGL(k_particle_fn_step<16>, grid, block, 0, st, a);
-    else if (a.D <= 24) hipLaunchKernelGGL(k_particle_fn_step<24>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(k_particle_fn_step<MAX_D>, grid, block, 0, st, a);
-}
-
 // [E][rows_pad][Ppad] on the device's side -> the caller's [P][E][rows]
 void fn_untranspose(const std::vector<double>& dev, double* out, int E, int rows, int rows_pad, int P, int Ppad) {
     for (int p = 0; p < P; ++p)
@@ -267,6 +137,123 @@ void fn_untranspose(const std::vector<double>& dev, double* out, int E, int rows
 }
 
 }  // namespace
+
+void launch_fn_step(hipStream_t st, const ParticleFnArgs& a, int count) {
+    const dim3 grid(round_up(count, 64) / 64, a.E), block(64 * FN_WAVES);
+    if (a.D <= 4) hipLaunchKernelGGL(k_particle_fn_step<4>, grid, block, 0, st, a);
+    else if (a.D <= 8) hipLaunchKernelGGL(k_particle_fn_step<8>, grid, block, 0, st, a);
+    else if (a.D <= 12) hipLaunchKernelGGL(k_particle_fn_step<12>, grid, block, 0, st, a);
+    else if (a.D <= 16) hipLaunchKernelGGL(k_particle_fn_step<16>, grid, block, 0, st, a);
+    else if (a.D <= 24) hipLaunchKernelGGL(k_particle_fn_step<24>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(k_particle_fn_step<MAX_D>, grid, block, 0, st, a);
+}
+
+int fn_plan(pilco_ctx* ctx, const char* who, const pilco_function_draws* draws, int P, FnPlan& pl) {
+    const Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    const std::string pre = std::string(who) + ": ";
+    if (s.M > 0) return fail(ctx, PILCO_E_STATE, pre + "the slot is sparse (FITC, M > 0); function samples need an exact GP");
+    if (!draws) return fail(ctx, PILCO_E_SHAPE, pre + "null draws");
+    const int L = draws->L;
+    if (L < 1 || L > PILCO_MAX_FN_FEATURES) return fail(ctx, PILCO_E_SHAPE, pre + "L must be in 1..4096");
+    const int given = (draws->omega != nullptr) + (draws->phase != nullptr) + (draws->w != nullptr) + (draws->xi != nullptr);
+    if (given != 0 && given != 4) return fail(ctx, PILCO_E_SHAPE, pre + "omega, phase, w and xi are given together or not at all");
+    pl.own = given == 4;
+    pl.E = s.E; pl.D = s.D; pl.N = s.N; pl.npad = s.Npad; pl.L = L; pl.Lpad = round_up(L, 64); pl.P = P; pl.Ppad = round_up(P, 64);
+    const size_t per_p = (size_t)pl.E * ((size_t)pl.Lpad + 2 * (size_t)pl.npad), budget = fn_budget();
+    if (per_p * pl.Ppad > budget) {
+        const long long fit = (long long)(budget / per_p / 64 * 64);
+        return fail(ctx, PILCO_E_SHAPE, pre + "E Ppad (Lpad + 2 npad) = " + std::to_string(per_p * pl.Ppad) +
+                                            " doubles exceed the budget of " + std::to_string(budget) +
+                                            " (PILCO_PARTICLE_FN_BUDGET); the largest P that fits is " + std::to_string(fit));
+    }
+    pl.n_om = (size_t)pl.E * L * pl.D; pl.n_ph = (size_t)pl.E * L;
+    pl.n_w = (size_t)P * pl.E * L; pl.n_xi = (size_t)P * pl.E * pl.N;
+    pl.n_Wt = (size_t)pl.E * pl.Lpad * pl.Ppad; pl.n_V = (size_t)pl.E * pl.npad * pl.Ppad;
+    return PILCO_OK;
+}
+
+int fn_setup(pilco_ctx* ctx, const FnPlan& pl, const pilco_function_draws* draws, const pilco_function_draws_out* draws_out,
+             unsigned long long seed) {
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    PredictWork& pw = *s.pred;
+    hipStream_t st = ctx->st;
+    const int E = pl.E, D = pl.D, N = pl.N, npad = pl.npad, L = pl.L, Lpad = pl.Lpad, P = pl.P, Ppad = pl.Ppad;
+    const bool own = pl.own, want_xi = draws_out && draws_out->xi && !own;
+    ENSURE(pw.fn_om, pl.n_om);
+    ENSURE(pw.fn_ph, pl.n_ph);
+    ENSURE(pw.fn_Wt, pl.n_Wt);
+    ENSURE(pw.fn_phix, (size_t)E * npad * Lpad);
+    ENSURE(pw.fn_R, pl.n_V);
+    ENSURE(pw.fn_V, pl.n_V);
+    if (want_xi) ENSURE(pw.fn_xi, pl.n_V);
+    if (own) {
+        ENSURE(pw.fn_raw, pl.n_w + pl.n_xi);
+        HIPCHK(hipMemcpyAsync(pw.fn_om.p, draws->omega, sizeof(double) * pl.n_om, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(pw.fn_ph.p, draws->phase, sizeof(double) * pl.n_ph, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(pw.fn_raw.p, draws->w, sizeof(double) * pl.n_w, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(pw.fn_raw.p + pl.n_w, draws->xi, sizeof(double) * pl.n_xi, hipMemcpyHostToDevice, st));
+    }
+    // set-up: features, weights, residuals, V
+    FnSetupArgs ua{};
+    ua.om = pw.fn_om.p; ua.ph = pw.fn_ph.p; ua.Wt = pw.fn_Wt.p; ua.PhiX = pw.fn_phix.p; ua.R = pw.fn_R.p;
+    ua.xi_out = want_xi ? pw.fn_xi.p : nullptr;
+    ua.w_in = own ? pw.fn_raw.p : nullptr;
+    ua.xi_in = own ? pw.fn_raw.p + pl.n_w : nullptr;
+    ua.Xt = s.Xt.p; ua.Yt = s.Yt.p; ua.ls = s.ls.p; ua.sf2 = s.var.p; ua.noise = s.noise.p;
+    ua.seed = seed; ua.E = E; ua.D = D; ua.N = N; ua.npad = npad; ua.L = L; ua.Lpad = Lpad; ua.P = P; ua.Ppad = Ppad;
+    if (!own) hipLaunchKernelGGL(k_fn_features, dim3((E * L + 255) / 256), dim3(256), 0, st, ua);
+    hipLaunchKernelGGL(k_fn_weights, dim3((Ppad + 255) / 256, Lpad), dim3(256), 0, st, ua);
+    hipLaunchKernelGGL(k_fn_phix, dim3((unsigned)(((long)npad * Lpad + 255) / 256), E), dim3(256), 0, st, ua);
+    GemmDesc g{};
+    g.alpha = 1.0; g.beta = 0.0;
+    g.A = pw.fn_phix.p; g.lda = Lpad; g.sA = (long)npad * Lpad;
+    g.B = pw.fn_Wt.p; g.ldb = Ppad; g.sB = (long)Lpad * Ppad;
+    g.C = pw.fn_R.p; g.ldc = Ppad; g.sC = (long)npad * Ppad;
+    g.M = npad; g.N = Ppad; g.K = Lpad;
+    launch_gemm(st, g, false, false, E);
+    hipLaunchKernelGGL(k_fn_resid, dim3((Ppad + 255) / 256, npad), dim3(256), 0, st, ua);
+    g.A = s.iK.p; g.lda = npad; g.sA = (long)npad * npad;
+    g.B = pw.fn_R.p; g.ldb = Ppad; g.sB = (long)npad * Ppad;
+    g.C = pw.fn_V.p;
+    g.K = npad;
+    launch_gemm(st, g, false, false, E);
+    return PILCO_OK;
+}
+
+int fn_draws_download(pilco_ctx* ctx, const FnPlan& pl, const pilco_function_draws_out* draws_out, FnDrawsStage& stage) {
+    if (!draws_out) return PILCO_OK;
+    PredictWork& pw = *ctx->slot[PILCO_SLOT_DYNAMICS].pred;
+    hipStream_t st = ctx->st;
+    if (draws_out->omega) HIPCHK(hipMemcpyAsync(draws_out->omega, pw.fn_om.p, sizeof(double) * pl.n_om, hipMemcpyDeviceToHost, st));
+    if (draws_out->phase) HIPCHK(hipMemcpyAsync(draws_out->phase, pw.fn_ph.p, sizeof(double) * pl.n_ph, hipMemcpyDeviceToHost, st));
+    if (draws_out->w && !pl.own) {
+        stage.w.resize(pl.n_Wt);
+        HIPCHK(hipMemcpyAsync(stage.w.data(), pw.fn_Wt.p, sizeof(double) * pl.n_Wt, hipMemcpyDeviceToHost, st));
+    }
+    if (draws_out->xi && !pl.own) {
+        stage.xi.resize(pl.n_V);
+        HIPCHK(hipMemcpyAsync(stage.xi.data(), pw.fn_xi.p, sizeof(double) * pl.n_V, hipMemcpyDeviceToHost, st));
+    }
+    if (draws_out->v) {
+        stage.v.resize(pl.n_V);
+        HIPCHK(hipMemcpyAsync(stage.v.data(), pw.fn_V.p, sizeof(double) * pl.n_V, hipMemcpyDeviceToHost, st));
+    }
+    return PILCO_OK;
+}
+
+void fn_draws_finish(const FnPlan& pl, const pilco_function_draws* draws, const pilco_function_draws_out* draws_out,
+                     const FnDrawsStage& stage) {
+    if (!draws_out) return;
+    if (draws_out->w) {
+        if (pl.own) memcpy(draws_out->w, draws->w, sizeof(double) * pl.n_w);
+        else fn_untranspose(stage.w, draws_out->w, pl.E, pl.L, pl.Lpad, pl.P, pl.Ppad);
+    }
+    if (draws_out->xi) {
+        if (pl.own) memcpy(draws_out->xi, draws->xi, sizeof(double) * pl.n_xi);
+        else fn_untranspose(stage.xi, draws_out->xi, pl.E, pl.N, pl.npad, pl.P, pl.Ppad);
+    }
+    if (draws_out->v) fn_untranspose(stage.v, draws_out->v, pl.E, pl.N, pl.npad, pl.P, pl.Ppad);
+}
 
 extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
                                           const double* x0, int P, int H, const double* eps, unsigned long long seed,
@@ -280,25 +267,9 @@ extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* po
     const int E = s.E, D = s.D, U = D - E;
     if (const char* why = event_table_refusal(events, n_events, counts, E))
         return fail(ctx, PILCO_E_SHAPE, std::string("rollout_particles_fn: ") + why);
-    if (s.M > 0)
-        return fail(ctx, PILCO_E_STATE, "rollout_particles_fn: the slot is sparse (FITC, M > 0); function samples need an exact GP");
-    if (!draws) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: null draws");
-    const int L = draws->L;
-    if (L < 1 || L > PILCO_MAX_FN_FEATURES) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: L must be in 1..4096");
-    const int given = (draws->omega != nullptr) + (draws->phase != nullptr) + (draws->w != nullptr) + (draws->xi != nullptr);
-    if (given != 0 && given != 4)
-        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: omega, phase, w and xi are given together or not at all");
-    const bool own = given == 4;
-    const int N = s.N, npad = s.Npad, Lpad = round_up(L, 64), Ppad = round_up(P, 64);
-    {
-        const size_t per_p = (size_t)E * ((size_t)Lpad + 2 * (size_t)npad), budget = fn_budget();
-        if (per_p * Ppad > budget) {
-            const long long fit = (long long)(budget / per_p / 64 * 64);
-            return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: E Ppad (Lpad + 2 npad) = " + std::to_string(per_p * Ppad) +
-                                                " doubles exceed the budget of " + std::to_string(budget) +
-                                                " (PILCO_PARTICLE_FN_BUDGET); the largest P that fits is " + std::to_string(fit));
-        }
-    }
+    FnPlan pl{};
+    if (int r = fn_plan(ctx, "rollout_particles_fn", draws, P, pl)) return r;
+    const int N = pl.N, npad = pl.npad, L = pl.L, Lpad = pl.Lpad, Ppad = pl.Ppad;
     HIPCHK(hipSetDevice(ctx->device));
     if (!s.factor_valid)
         if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
@@ -310,9 +281,6 @@ extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* po
     const int Q = E + E * E + 1, nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
     const int nslab = particles ? H + 1 : 2;
     const bool keep_eps = noisy && H > 0 && (eps || eps_out);
-    const bool want_xi = draws_out && draws_out->xi && !own;
-    const size_t n_om = (size_t)E * L * D, n_ph = (size_t)E * L, n_w = (size_t)P * E * L, n_xi = (size_t)P * E * N;
-    const size_t n_Wt = (size_t)E * Lpad * Ppad, n_V = (size_t)E * npad * Ppad;
     std::vector<double> hp(particle_par_doubles(E, U), 0.0);
     std::vector<double> hstats((size_t)(H + 1) * Q);
     ENSURE(pw.Xt, (size_t)D * Ppad);
@@ -322,14 +290,6 @@ extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* po
     ENSURE(pw.pt_part, (size_t)nblk * Q);
     ENSURE(pw.pt_stats, hstats.size());
     ENSURE(pw.pt_par, hp.size());
-    ENSURE(pw.fn_om, n_om);
-    ENSURE(pw.fn_ph, n_ph);
-    ENSURE(pw.fn_Wt, n_Wt);
-    ENSURE(pw.fn_phix, (size_t)E * npad * Lpad);
-    ENSURE(pw.fn_R, n_V);
-    ENSURE(pw.fn_V, n_V);
-    if (want_xi) ENSURE(pw.fn_xi, n_V);
-    if (own) ENSURE(pw.fn_raw, n_w + n_xi);
     const int K = n_events;
     const size_t fh_bytes = sizeof(int) * (size_t)P * K;
     if (K > 0) {
@@ -349,40 +309,10 @@ extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* po
     HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
     if (keep_eps && eps) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
-    if (own) {
-        HIPCHK(hipMemcpyAsync(pw.fn_om.p, draws->omega, sizeof(double) * n_om, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(pw.fn_ph.p, draws->phase, sizeof(double) * n_ph, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(pw.fn_raw.p, draws->w, sizeof(double) * n_w, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(pw.fn_raw.p + n_w, draws->xi, sizeof(double) * n_xi, hipMemcpyHostToDevice, st));
-    }
-
-    // set-up: features, weights, residuals, V
-    FnSetupArgs ua{};
-    ua.om = pw.fn_om.p; ua.ph = pw.fn_ph.p; ua.Wt = pw.fn_Wt.p; ua.PhiX = pw.fn_phix.p; ua.R = pw.fn_R.p;
-    ua.xi_out = want_xi ? pw.fn_xi.p : nullptr;
-    ua.w_in = own ? pw.fn_raw.p : nullptr;
-    ua.xi_in = own ? pw.fn_raw.p + n_w : nullptr;
-    ua.Xt = s.Xt.p; ua.Yt = s.Yt.p; ua.ls = s.ls.p; ua.sf2 = s.var.p; ua.noise = s.noise.p;
-    ua.seed = seed; ua.E = E; ua.D = D; ua.N = N; ua.npad = npad; ua.L = L; ua.Lpad = Lpad; ua.P = P; ua.Ppad = Ppad;
-    if (!own) hipLaunchKernelGGL(k_fn_features, dim3((E * L + 255) / 256), dim3(256), 0, st, ua);
-    hipLaunchKernelGGL(k_fn_weights, dim3((Ppad + 255) / 256, Lpad), dim3(256), 0, st, ua);
-    hipLaunchKernelGGL(k_fn_phix, dim3((unsigned)(((long)npad * Lpad + 255) / 256), E), dim3(256), 0, st, ua);
-    GemmDesc g{};
-    g.alpha = 1.0; g.beta = 0.0;
-    g.A = pw.fn_phix.p; g.lda = Lpad; g.sA = (long)npad * Lpad;
-    g.B = pw.fn_Wt.p; g.ldb = Ppad; g.sB = (long)Lpad * Ppad;
-    g.C = pw.fn_R.p; g.ldc = Ppad; g.sC = (long)npad * Ppad;
-    g.M = npad; g.N = Ppad; g.K = Lpad;
-    launch_gemm(st, g, false, false, E);
-    hipLaunchKernelGGL(k_fn_resid, dim3((Ppad + 255) / 256, npad), dim3(256), 0, st, ua);
-    g.A = s.iK.p; g.lda = npad; g.sA = (long)npad * npad;
-    g.B = pw.fn_R.p; g.ldb = Ppad; g.sB = (long)npad * Ppad;
-    g.C = pw.fn_V.p;
-    g.K = npad;
-    launch_gemm(st, g, false, false, E);
+    if (int r = fn_setup(ctx, pl, draws, draws_out, seed)) return r;
 
     fa.E = E; fa.D = D; fa.N = N; fa.npad = npad; fa.L = L; fa.Lpad = Lpad; fa.P = P; fa.Ppad = Ppad; fa.seed = seed;
-    fa.Xq = pw.Xt.p; fa.Xt = s.Xt.p; fa.ls = s.ls.p; fa.sf2 = s.var.p;
+    fa.Xq = pw.Xt.p; fa.ldq = Ppad; fa.Xt = s.Xt.p; fa.ls = s.ls.p; fa.sf2 = s.var.p;
     fa.noise = noisy ? s.noise.p : nullptr;
     fa.om = pw.fn_om.p; fa.ph = pw.fn_ph.p; fa.Wt = pw.fn_Wt.p; fa.V = pw.fn_V.p;
     fa.rew = pw.pt_rew.p;
@@ -420,7 +350,7 @@ extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* po
         fa.eps_in = (noisy && eps) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
         fa.eps_out = (noisy && !eps && eps_out) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
         launch_particle_head(st, ha);
-        launch_fn_step(st, fa);
+        launch_fn_step(st, fa, P);
         stats(t + 1, true);
         count_events(t + 1);
     }
@@ -433,36 +363,11 @@ extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* po
         HIPCHK(hipMemcpyAsync(counts, pw.pt_ev_counts.p, sizeof(long long) * (H + 1) * K, hipMemcpyDeviceToHost, st));
         if (first_hit) HIPCHK(hipMemcpyAsync(first_hit, pw.pt_ev_first.p, fh_bytes, hipMemcpyDeviceToHost, st));
     }
-    std::vector<double> h_w, h_xi, h_v;
-    if (draws_out) {
-        if (draws_out->omega) HIPCHK(hipMemcpyAsync(draws_out->omega, pw.fn_om.p, sizeof(double) * n_om, hipMemcpyDeviceToHost, st));
-        if (draws_out->phase) HIPCHK(hipMemcpyAsync(draws_out->phase, pw.fn_ph.p, sizeof(double) * n_ph, hipMemcpyDeviceToHost, st));
-        if (draws_out->w && !own) {
-            h_w.resize(n_Wt);
-            HIPCHK(hipMemcpyAsync(h_w.data(), pw.fn_Wt.p, sizeof(double) * n_Wt, hipMemcpyDeviceToHost, st));
-        }
-        if (want_xi) {
-            h_xi.resize(n_V);
-            HIPCHK(hipMemcpyAsync(h_xi.data(), pw.fn_xi.p, sizeof(double) * n_V, hipMemcpyDeviceToHost, st));
-        }
-        if (draws_out->v) {
-            h_v.resize(n_V);
-            HIPCHK(hipMemcpyAsync(h_v.data(), pw.fn_V.p, sizeof(double) * n_V, hipMemcpyDeviceToHost, st));
-        }
-    }
+    FnDrawsStage stage;
+    if (int r = fn_draws_download(ctx, pl, draws_out, stage)) return r;
     HIPCHK(hipStreamSynchronize(st));
     if (noisy && eps_out && eps && H > 0) memcpy(eps_out, eps, sizeof(double) * H * PE);
-    if (draws_out) {
-        if (draws_out->w) {
-            if (own) memcpy(draws_out->w, draws->w, sizeof(double) * n_w);
-            else fn_untranspose(h_w, draws_out->w, E, L, Lpad, P, Ppad);
-        }
-        if (draws_out->xi) {
-            if (own) memcpy(draws_out->xi, draws->xi, sizeof(double) * n_xi);
-            else fn_untranspose(h_xi, draws_out->xi, E, N, npad, P, Ppad);
-        }
-        if (draws_out->v) fn_untranspose(h_v, draws_out->v, E, N, npad, P, Ppad);
-    }
+    fn_draws_finish(pl, draws, draws_out, stage);
     for (int t = 0; t <= H; ++t) {
         const double* row = &hstats[(size_t)t * Q];
         memcpy(mean + (size_t)t * E, row, sizeof(double) * E);

@@ -28,7 +28,6 @@
 namespace pilco {
 
 constexpr size_t PG_BUDGET = size_t(1) << 27;   // doubles of stored step matrices per group (1 GiB)
-constexpr int PG_RB = 64;                       // particles (threads) per workgroup of the reverse kernel
 
 struct PgFoldArgs {
     const double *dmean, *dvar;   // [E][ldt][D] of the chunk
@@ -64,19 +63,6 @@ __global__ __launch_bounds__(64) void k_pg_reward_partials(const double* rew, do
     for (int k = 0; k < PT_BLOCK; ++k) s += (p0 + k < P) ? rew[p0 + k] : 0.0;
     part[(long)(b0 + b) * H + t] = s;
 }
-
-struct PgReverseArgs {
-    ParticleHeadArgs pol;   // the policy (x: the states of step t, [P][E]; p0: the group's first particle; ntc: its particles)
-    const double* A;        // [E][D][ldg] the step's matrices, or nullptr: lam_in is zero (t = H - 1)
-    const double* lam_in;   // [E][ldg]
-    double* lam_out;        // [E][ldg]
-    double* ds;             // [U][ldg] cotangents of the sines' arguments
-    int ldg, n_rewards;
-    ParticleReward rw[MAX_REWARD_TERMS];
-};
-
-// dynamic LDS: [3 E + U][PG_RB] the particle's lam, x, lam' and g_u / ds (a column per thread), then 1 / lengthscale [U][E]
-inline int pg_reverse_lds_doubles(int E, int U) { return (3 * E + U) * PG_RB + U * E; }
 
 __global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) {
     extern __shared__ double pg_lds[];
@@ -170,16 +156,6 @@ __global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) {
     for (int e = 0; e < E; ++e) a.lam_out[(long)e * ldg + l] = ln[e * PG_RB];
 }
 
-struct PgParamArgs {
-    ParticleHeadArgs pol;   // as PgReverseArgs
-    const double* ds;       // [U][ldg]
-    double* part;           // [blocks of all particles][Q] the blocks' cells
-    int ldg, Q;
-};
-
-// quantities of a policy: LinearController dW [U][E] | db [U]; RbfController dbeta [U][bf] | dC [bf][E] | dl [U][E]
-inline int pg_quantities(int kind, int E, int U, int bf) { return kind == PILCO_POLICY_RBF ? U * bf + bf * E + U * E : U * E + U; }
-
 // block b of the group: particles PT_BLOCK b .. ; thread q adds quantity q over them in index order
 __global__ __launch_bounds__(PT_BLOCK) void k_pg_param_partials(PgParamArgs a) {
     const ParticleHeadArgs& po = a.pol;
@@ -257,15 +233,32 @@ __global__ __launch_bounds__(PT_BLOCK) void k_pg_finish(const double* part, doub
 
 using namespace pilco;
 
-namespace {
-
-size_t group_budget() {
+size_t pg_group_budget() {
     if (const char* v = getenv("PILCO_PARTICLE_GRAD_BUDGET")) {
         const long long n = atoll(v);
         if (n > 0) return (size_t)n;
     }
     return PG_BUDGET;
 }
+
+void launch_pg_reward_partials(hipStream_t st, const double* rew, double* part, int P, int b0, int nb, int t, int H) {
+    hipLaunchKernelGGL(k_pg_reward_partials, dim3((nb + 63) / 64), dim3(64), 0, st, rew, part, P, b0, nb, t, H);
+}
+
+void launch_pg_reverse(hipStream_t st, const PgReverseArgs& a) {
+    const int lds_bytes = (int)sizeof(double) * pg_reverse_lds_doubles(a.pol.E, a.pol.U);
+    hipLaunchKernelGGL(k_pg_reverse, dim3((a.pol.ntc + PG_RB - 1) / PG_RB), dim3(PG_RB), lds_bytes, st, a);
+}
+
+void launch_pg_param_partials(hipStream_t st, const PgParamArgs& a) {
+    hipLaunchKernelGGL(k_pg_param_partials, dim3((a.pol.ntc + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, a);
+}
+
+void launch_pg_finish(hipStream_t st, const double* part, double* out, int nblk, int Q, int P) {
+    hipLaunchKernelGGL(k_pg_finish, dim3((Q + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, part, out, nblk, Q, P);
+}
+
+namespace {
 
 // Both entry points.  par: LinearController dW (U,E) | db (U); RbfController dbeta (U,bf) | dC (bf,E) | dl (U,E), over P.
 int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0,
@@ -294,8 +287,8 @@ int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pil
     // the groups: a multiple of PT_BLOCK particles whose matrices fit the budget (at least one block)
     const size_t per_particle = (size_t)(H - 1) * E * D;
     int Pg = P;
-    if (per_particle * (size_t)P > group_budget())
-        Pg = (int)std::min<size_t>((size_t)round_up(P, PT_BLOCK), std::max<size_t>(1, group_budget() / per_particle / PT_BLOCK) * PT_BLOCK);
+    if (per_particle * (size_t)P > pg_group_budget())
+        Pg = (int)std::min<size_t>((size_t)round_up(P, PT_BLOCK), std::max<size_t>(1, pg_group_budget() / per_particle / PT_BLOCK) * PT_BLOCK);
     const int ldg = round_up(std::min(Pg, P), 64);
     const int ntc_max = std::min(ldg, predict_chunk_cap(E, npad));
     std::vector<double> hp(particle_par_doubles(E, U), 0.0);
@@ -340,7 +333,6 @@ int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pil
     fa.noise = ta.noise; fa.ldg = ldg; fa.E = E; fa.D = D;
     PgParamArgs pa{};
     pa.ds = ra.ds = pw.pg_ds.p; pa.part = pw.pg_part.p; pa.ldg = ra.ldg = ldg; pa.Q = Q;
-    const int lds_bytes = (int)sizeof(double) * pg_reverse_lds_doubles(E, U);
     auto slab = [&](int t) { return pw.pt_x.p + (size_t)t * PE; };
     for (int g0 = 0; g0 < P; g0 += Pg) {
         const int ng = std::min(Pg, P - g0), nbg = (ng + PT_BLOCK - 1) / PT_BLOCK;
@@ -368,8 +360,7 @@ int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pil
                 fa.p0 = p0; fa.l0 = l0; fa.ntc = ntc; fa.ldt = ldt;
                 hipLaunchKernelGGL(k_pg_fold, dim3((ntc + 255) / 256, E), dim3(256), 0, st, fa);
             }
-            hipLaunchKernelGGL(k_pg_reward_partials, dim3((nbg + 63) / 64), dim3(64), 0, st, (const double*)pw.pt_rew.p,
-                               pw.pg_rew.p, P, g0 / PT_BLOCK, nbg, t, H);
+            launch_pg_reward_partials(st, pw.pt_rew.p, pw.pg_rew.p, P, g0 / PT_BLOCK, nbg, t, H);
         }
         ra.pol.p0 = g0; ra.pol.ntc = ng;
         for (int t = H - 1; t >= 0; --t) {
@@ -378,10 +369,10 @@ int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pil
             ra.A = t < H - 1 ? pw.pg_A.p + (size_t)t * E * D * ldg : nullptr;
             ra.lam_in = pw.pg_lam.p + (size_t)in * E * ldg;
             ra.lam_out = pw.pg_lam.p + (size_t)(in ^ 1) * E * ldg;
-            hipLaunchKernelGGL(k_pg_reverse, dim3((ng + PG_RB - 1) / PG_RB), dim3(PG_RB), lds_bytes, st, ra);
+            launch_pg_reverse(st, ra);
             if (Q > 0 && t < H - 1) {
                 pa.pol = ra.pol;
-                hipLaunchKernelGGL(k_pg_param_partials, dim3(nbg), dim3(PT_BLOCK), 0, st, pa);
+                launch_pg_param_partials(st, pa);
             }
         }
         HIPCHK(hipGetLastError());
@@ -394,11 +385,8 @@ int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pil
         }
     }
     // the rewards of the steps as k_particle_finish has them, and the parameter sums: one download, one synchronisation
-    hipLaunchKernelGGL(k_pg_finish, dim3((H + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, (const double*)pw.pg_rew.p, pw.pg_out.p,
-                       nblk, H, P);
-    if (Q > 0)
-        hipLaunchKernelGGL(k_pg_finish, dim3((Q + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, (const double*)pw.pg_part.p,
-                           pw.pg_out.p + H, nblk, Q, P);
+    launch_pg_finish(st, pw.pg_rew.p, pw.pg_out.p, nblk, H, P);
+    if (Q > 0) launch_pg_finish(st, pw.pg_part.p, pw.pg_out.p + H, nblk, Q, P);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(hout.data(), pw.pg_out.p, sizeof(double) * hout.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -410,26 +398,26 @@ int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pil
     return PILCO_OK;
 }
 
+}  // namespace
+
 // the refusals of both entry points, before any launch or upload
-int check_grad_call(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0, int P,
+int check_particle_grad_call(pilco_ctx* ctx, const char* who, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0, int P,
                     int H, const double* reward, bool rbf) {
     if (int r = check_particle_state(ctx, P, H)) return r;
-    if (!x0 || !reward) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad: null x0 or reward");
+    if (!x0 || !reward) return fail(ctx, PILCO_E_SHAPE, std::string(who) + ": null x0 or reward");
     if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
     if (rbf != (policy->kind == PILCO_POLICY_RBF))
-        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad: no policy or a LinearController (pilco_rollout_particles_grad), an "
-                                        "RbfController (pilco_rollout_particles_grad_rbf)");
+        return fail(ctx, PILCO_E_SHAPE, std::string(who) + ": no policy or a LinearController (pilco_" + who + "), an "
+                                        "RbfController (pilco_" + who + "_rbf)");
     return PILCO_OK;
 }
-
-}  // namespace
 
 extern "C" int pilco_rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
                                             const double* x0, int P, int H, const double* eps, unsigned long long seed,
                                             int observation_noise, double* reward, double* reward_steps, double* dW, double* db,
                                             double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
-    if (int r = check_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, false)) return r;
+    if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, false)) return r;
     if (policy->kind == PILCO_POLICY_LINEAR && (!dW || !db)) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad: null dW or db");
     std::vector<double> par;
     if (int r = rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
@@ -449,7 +437,7 @@ extern "C" int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_poli
                                                 const double* lsp, const double* noisep, int bf, double* reward, double* reward_steps,
                                                 double* dX, double* dY, double* dls, double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
-    if (int r = check_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, true)) return r;
+    if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, true)) return r;
     if (!Xp || !Yp || !lsp || !noisep || !dX || !dY || !dls)
         return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad_rbf: null policy parameters or null dX, dY or dls");
     if (bf != ctx->slot[PILCO_SLOT_POLICY].N)

@@ -205,8 +205,17 @@ class PILCO:
         root = (V * np.sqrt(np.clip(w, 0.0, None))) @ V.T
         return m + np.random.default_rng(seed).standard_normal((int(num_particles), E)) @ root
 
+    def _check_particle_dynamics(self, who, dynamics):
+        """the dynamics argument of the particle methods, before any device call"""
+        if dynamics not in ("marginal", "function"):
+            raise ValueError("%s: dynamics must be 'marginal' or 'function', got %r" % (who, dynamics))
+        if dynamics == "function" and isinstance(self.mgpr, SMGPR):
+            raise NotImplementedError("%s: dynamics='function' needs an exact GP (MGPR); function samples of a "
+                                      "sparse model are not supported" % who)
+
     def particle_value_and_gradient(self, m_x=None, s_x=None, n=None, num_particles=1000, seed=0, eps=None, x0=None,
-                                    observation_noise=False, return_dx0=False):
+                                    observation_noise=False, return_dx0=False, dynamics="marginal", num_features=512,
+                                    function_draws=None):
         """Extension: (reward, grads) of the PARTICLE return -- sample_trajectories(...).reward_steps.sum() on the same initial
         particles and draws -- w.r.t. the controller parameters, on the device (pilco_rollout_particles_grad / _grad_rbf;
         docs/particle_gradients.md).  grads has the structure value_and_gradient returns: (dW, db) for a LinearController,
@@ -214,7 +223,11 @@ class PILCO:
         horizon; x0, eps, seed and observation_noise are those of sample_trajectories.  With x0 (or seed) and the draws fixed
         the value is a deterministic, smooth function of the parameters (common random numbers).  return_dx0: a third
         result (P, E), row p the gradient of particle p's own return w.r.t. its initial state.  Any reward term evaluated on
-        the host raises NotImplementedError, event terms included: an indicator has no gradient."""
+        the host raises NotImplementedError, event terms included: an indicator has no gradient.
+        dynamics="function": the return of sample_trajectories(dynamics="function") on num_features features or the caller's
+        function_draws (pilco_rollout_particles_fn_grad / _grad_rbf; docs/particle_fn_gradients.md); eps is then read only
+        with observation_noise.  Exact GP only: an SMGPR raises NotImplementedError.  Any other value raises ValueError."""
+        self._check_particle_dynamics("particle_value_and_gradient", dynamics)
         if self._host_reward_terms():
             raise NotImplementedError("particle_value_and_gradient: reward terms evaluated on the host (events included) are not "
                                       "part of the differentiated objective")
@@ -231,7 +244,18 @@ class PILCO:
         self.mgpr._user_factors = None
         self.mgpr._ensure_factorized()
         kw = dict(eps=eps, seed=seed, observation_noise=observation_noise, want_dx0=return_dx0)
-        if ctl is None or linear:
+        if dynamics == "function":
+            if function_draws is not None:
+                function_draws = {k: function_draws[k] for k in ("omega", "phase", "w", "xi")}
+            kw.update(num_features=num_features, function_draws=function_draws)
+            if ctl is None or linear:
+                r, _, dW, db, dx0, _ = self.ctx.rollout_particles_fn_grad(self._policy_spec(), self._reward_terms(), x0, n, **kw)
+                grads = (dW.reshape(ctl.W.shape), db.reshape(ctl.b.shape)) if linear else ()
+            else:
+                r, _, dX, dY, dl, dx0, _ = self.ctx.rollout_particles_fn_grad_rbf(self._policy_spec(), self._reward_terms(), x0, n,
+                                                                                  ctl.X, ctl.Y, ctl.lengthscales, ctl.noise, **kw)
+                grads = (dX, dY, dl)
+        elif ctl is None or linear:
             r, _, dW, db, dx0 = self.ctx.rollout_particles_grad(self._policy_spec(), self._reward_terms(), x0, n, **kw)
             grads = (dW.reshape(ctl.W.shape), db.reshape(ctl.b.shape)) if linear else ()
         else:
@@ -318,11 +342,7 @@ class PILCO:
         reproduces every output bitwise) -- and follows it deterministically (pilco_rollout_particles_fn,
         docs/particle_functions.md); eps is then used only with observation_noise (the result's eps is None without it).
         Exact GP only: an SMGPR raises NotImplementedError.  Any other value raises ValueError."""
-        if dynamics not in ("marginal", "function"):
-            raise ValueError("sample_trajectories: dynamics must be 'marginal' or 'function', got %r" % (dynamics,))
-        if dynamics == "function" and isinstance(self.mgpr, SMGPR):
-            raise NotImplementedError("sample_trajectories: dynamics='function' needs an exact GP (MGPR); function samples of a "
-                                      "sparse model are not supported")
+        self._check_particle_dynamics("sample_trajectories", dynamics)
         host = self._host_reward_terms()
         if any(not hasattr(r, "event_spec") for _, r in host):
             raise NotImplementedError("sample_trajectories: reward terms evaluated on the host are not supported on particles; "

@@ -595,12 +595,13 @@ def _optimize_policy_lanes(pilco, maxiter, restarts, verbose, seeded=False):
     return best_r
 
 
-def particle_loss_and_grad(pilco, u, put, x0, seed, observation_noise):
+def particle_loss_and_grad(pilco, u, put, x0, seed, observation_noise, dynamics="marginal", num_features=512):
     """-J and its gradient for the particle return on the fixed initial particles x0 and the draws of `seed`
     (PILCO.particle_value_and_gradient)."""
     from .controllers import LinearController
     put(u)
-    r, grads = pilco.particle_value_and_gradient(x0=x0, seed=seed, observation_noise=observation_noise)
+    r, grads = pilco.particle_value_and_gradient(x0=x0, seed=seed, observation_noise=observation_noise, dynamics=dynamics,
+                                                 num_features=num_features)
     if isinstance(pilco.controller, LinearController):
         Wb, bb = grads
         return -r, -np.concatenate([Wb.ravel(), bb.ravel()])
@@ -614,19 +615,23 @@ def optimize_policy(pilco, maxiter=50, restarts=1, verbose=True, objective="mome
     same L-BFGS-B walk on minus the particle return (common random numbers: the initial particles and the seed of the draws
     are fixed over the whole walk and over the restarts, so the objective is deterministic and smooth); the restarts run one
     after the other and are compared by their particle return.  particle_options: num_particles (1000), seed (0),
-    observation_noise (False)."""
+    observation_noise (False), dynamics ("marginal"; "function": the return over posterior function samples,
+    docs/particle_fn_gradients.md) and num_features (512, with dynamics="function").  The function draws are those of `seed`,
+    generated on the device at every evaluation: the same functions over the walk and over the restarts, like x0."""
     if objective not in ("moment_matching", "particles"):
         raise ValueError("optimize_policy: objective is 'moment_matching' or 'particles'")
     if pilco.controller is None:
         raise ValueError("optimize_policy: the model has no controller (control_dim == 0)")
     particles = objective == "particles"
     if particles:
-        opts = dict(num_particles=1000, seed=0, observation_noise=False)
+        opts = dict(num_particles=1000, seed=0, observation_noise=False, dynamics="marginal", num_features=512)
         unknown = set(particle_options or {}) - set(opts)
         if unknown:
             raise ValueError("optimize_policy: unknown particle_options %s" % sorted(unknown))
         opts.update(particle_options or {})
         seed, obs = int(opts["seed"]), bool(opts["observation_noise"])
+        pkw = dict(dynamics=opts["dynamics"], num_features=int(opts["num_features"]))
+        pilco._check_particle_dynamics("optimize_policy", pkw["dynamics"])
         x0 = pilco._initial_particles(pilco.m_init, pilco.S_init, opts["num_particles"], seed)
     elif particle_options is not None:
         raise ValueError("optimize_policy: particle_options go with objective='particles'")
@@ -637,7 +642,7 @@ def optimize_policy(pilco, maxiter=50, restarts=1, verbose=True, objective="mome
 
     def loss(u):
         if particles:
-            return particle_loss_and_grad(pilco, u, put, x0, seed, obs)
+            return particle_loss_and_grad(pilco, u, put, x0, seed, obs, **pkw)
         return policy_loss_and_grad(pilco, u, put)
 
     def run():
@@ -645,7 +650,7 @@ def optimize_policy(pilco, maxiter=50, restarts=1, verbose=True, objective="mome
         res = minimize(loss, get(), jac=True, method="L-BFGS-B", options=dict(maxiter=maxiter))
         put(res.x)
         if particles:
-            r = float(pilco.particle_value_and_gradient(x0=x0, seed=seed, observation_noise=obs)[0])
+            r = float(pilco.particle_value_and_gradient(x0=x0, seed=seed, observation_noise=obs, **pkw)[0])
         else:
             r = float(pilco.compute_reward()[0, 0])
         if verbose:
