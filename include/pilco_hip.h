@@ -116,6 +116,33 @@ int pilco_gp_predict_points(pilco_ctx* ctx, int slot, const double* Xs, int Nt, 
  * fixed order that depends on its own coordinates only: the same bits alone, in any batch and for one output or all. */
 int pilco_gp_predict_points_jac(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int output, const double* Z_all,
                                 double* mean, double* var, double* dmean, double* dvar);
+/* The full posterior covariance between the test points (GPflow predict_f with full_cov=True; docs/predict_cov.md):
+ *   cov (E, Nt, Nt), output-major:  cov_e[a][b] = k_e(x_a, x_b) - w_a . w_b,  w_a = L^{-1} k*(x_a)
+ *   (FITC: - w0_a . w0_b + sn2 w1_a . w1_b with w0 = Luu^{-1} ku*, w1 = iAt ku*).
+ * mean (E, Nt) may be NULL; where given it holds the bits pilco_gp_predict_points returns.  Arguments and refusals as for
+ * pilco_gp_predict_points, and PILCO_E_SHAPE when the call's footprint -- (operators + 1) E Ntpad npad doubles of cross-
+ * covariances and products plus E Ntpad^2 of covariance, Ntpad = Nt rounded up to 64 -- exceeds the budget (2^30 doubles;
+ * environment variable PILCO_PREDICT_COV_BUDGET): the message names the largest Nt that fits.  Not chunked over test points.
+ * Bit contracts: cov_e is symmetric to the bit; cov_e[a][b] depends on x_a, x_b and the model only -- not on Nt, not on
+ * where the two points stand among the test points, not on whether the output is computed alone or with the others; run to
+ * run the bits are identical.  The diagonal agrees with pilco_gp_predict_points' var within rounding, NOT to the bit: that
+ * kernel sums the squares in an order of its own. */
+int pilco_gp_predict_points_cov(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int output, const double* Z_all,
+                                double* mean, double* cov);
+/* Joint samples of the latent functions at the test points (GPflow predict_f_samples with full_cov=True):
+ *   samples (S, Nt, E):  f[s][a][e] = mean_e[a] + (C_e z[s][.][e])_a,   C_e C_e^T = cov_e + jitter I   (C_e lower triangular).
+ * z_in (S, Nt, E) are the caller's standard normals; NULL: drawn on the device, Philox domain 5 -- counter {s, a, j, 5}
+ * gives the normals of outputs 2j, 2j + 1 of sample s at test point a, so a draw depends on (seed, s, a, e) only.
+ * mean (E, Nt), cov (E, Nt, Nt), chol (E, Nt, Nt: C_e with zeros above the diagonal) and z_out (S, Nt, E: the normals used)
+ * are outputs and may each be NULL; for one output (0 <= output < E) read E = 1 in these shapes.  mean and cov hold the
+ * bits of pilco_gp_predict_points_cov; a sample's bits do not depend on S.  Everything is enqueued in one pass: one download,
+ * one synchronisation.  Refusals of pilco_gp_predict_points_cov (the budget counts three E Ntpad^2 matrices and the
+ * normals), PILCO_E_SHAPE for S <= 0 or a jitter that is negative or not finite; PILCO_E_NOT_PD when a pivot of some
+ * cov_e + jitter I is not positive (the message names the output, pilco_last_not_pd_output returns it): nothing is written
+ * to the caller's arrays then. */
+int pilco_gp_sample_points(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int output, const double* Z_all, int S,
+                           unsigned long long seed, const double* z_in, double jitter, double* samples, double* mean,
+                           double* cov, double* chol, double* z_out);
 
 /* ------------------------------------------------------------------ rollout */
 typedef enum pilco_policy_kind {

@@ -130,6 +130,13 @@ int pilco_debug_sk_pair_waves(int k, int waves, int nd, int tdiag, int toff, int
 #define PILCO_SK_PROBE_HEAD 10
 #define PILCO_SK_PROBE_WORDS 9
 int pilco_debug_sk_cut_probe(pilco_ctx* ctx, int* out, int n);
+/* Developer measurement (tools/predict_cov_bench.py; -DPILCO_DEV builds only, PILCO_E_STATE otherwise): the covariance
+ * kernel of pilco_gp_predict_points_cov alone, and the same matrix put together from the kernels it replaces -- launch_gram
+ * for K**, launch_gemm for W W^T (symmetric tiles; twice for FITC), one elementwise add --, `reps` times each between
+ * events on the context's stream: ms per repetition.  max_diff: the largest |difference| of the two matrices over the real
+ * block of every output.  Arguments and refusals as for pilco_gp_predict_points_cov (all outputs, the slot's own Z). */
+int pilco_debug_predict_cov_timed(pilco_ctx* ctx, int slot, const double* Xs, int Nt, int reps, float* ms_fused, float* ms_parts,
+                                  double* max_diff);
 /* Time `reps` factorisations (invalidating the cache each time): ms per factorisation. */
 int pilco_factorize_timed(pilco_ctx* ctx, int slot, int reps, float* ms_each);
 

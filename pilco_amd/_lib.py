@@ -71,6 +71,30 @@ def event_spec_of(ev):
     return spec
 
 
+def philox_cov_normals(seed, S, Nt, outputs):
+    """Host restatement of Philox domain 5 (csrc/philox_normal.h): the standard normals pilco_gp_sample_points draws for
+    (seed, sample s, test point a, output e), (S, Nt, len(outputs)).  Counter {s, a, e >> 1, 5}, key {seed & 2^32 - 1,
+    seed >> 32}, half e & 1 of the Box-Muller pair.  The words are the device's; log, cos and sin are NumPy's, so a draw
+    agrees with the device's to the rounding of those three functions.  Used for the marginal (full_cov=False) samples of
+    predict_f_samples, which need no covariance and so no device call beyond predict_f."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    outputs = np.asarray(list(outputs), np.uint64)
+    u = np.uint64
+    s, a, e = np.meshgrid(np.arange(S, dtype=np.uint64), np.arange(Nt, dtype=np.uint64), outputs, indexing="ij")
+    c0, c1, c2, c3 = s, a, e >> u(1), np.full(s.shape, 5, np.uint64)
+    k0, k1, m32 = seed & 0xFFFFFFFF, seed >> 32, u(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = u(0xD2511F53) * c0, u(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> u(32)) ^ c1 ^ u(k0), p1 & m32, (p0 >> u(32)) ^ c3 ^ u(k1), p0 & m32
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    n1 = (c0 >> u(5)) * u(1 << 26) + (c1 >> u(6))
+    n2 = (c2 >> u(5)) * u(1 << 26) + (c3 >> u(6))
+    u1 = (u(1 << 53) - n1).astype(np.float64) / float(1 << 53)
+    u2 = n2.astype(np.float64) / float(1 << 53)
+    r, ang = np.sqrt(-2.0 * np.log(u1)), 6.283185307179586476925 * u2
+    return np.where((e & u(1)) == 1, r * np.sin(ang), r * np.cos(ang))
+
+
 # every symbol include/pilco_hip.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 # pilco_seed_fn (include/pilco_hip.h): (user, H, E, traj [H+1][E+E*E], seeds [H+1][E+E*E]) -> None
@@ -103,6 +127,9 @@ SIGNATURES = {
     "pilco_gp_predict": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "pilco_gp_predict_points": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "pilco_gp_predict_points_jac": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_gp_predict_points_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "pilco_gp_sample_points": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_ulonglong, _dp, C.c_double,
+                                         _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                 _dp, _dp, _dp, _dp]),
     "pilco_rollout_particles": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
@@ -152,6 +179,8 @@ SIGNATURES = {
                                       C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_float),
                                       C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "pilco_factorize_timed": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "pilco_debug_predict_cov_timed": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                C.POINTER(C.c_double)]),
     "pilco_set_pair_timing": (C.c_int, [_vp, C.c_int]),
     "pilco_get_pair_timing": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "pilco_debug_timestamps": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
@@ -416,6 +445,52 @@ class Context:
         self._chk(self.lib.pilco_gp_predict_points_jac(self.h, slot, _ptr(Xs), Nt, int(output), _ptr(Za), _ptr(mean), _ptr(var),
                                                        _ptr(dmean), _ptr(dvar)))
         return mean, var, dmean, dvar
+
+    def _points_args(self, Xs, D, E, Z_all):
+        Xs = _f64(Xs)
+        if Xs.ndim != 2 or Xs.shape[1] != D:
+            raise ValueError(f"test inputs must be (Nt, {D})")
+        Za = None
+        if Z_all is not None:
+            Za = _f64(Z_all)
+            Za = _f64(Za, (E, Za.shape[-2], D))
+        return Xs, Za
+
+    def gp_predict_points_cov(self, slot, Xs, D, E, output=-1, Z_all=None):
+        """GPR / GPRFITC predict_f with full_cov=True at Xs (Nt, D): (mean (E, Nt) with the bits of gp_predict_points,
+        cov (E, Nt, Nt)), one row / matrix for 0 <= output < E (include/pilco_hip.h: pilco_gp_predict_points_cov)."""
+        Xs, Za = self._points_args(Xs, D, E, Z_all)
+        Nt = Xs.shape[0]
+        rows = E if output < 0 else 1
+        mean, cov = np.empty((rows, Nt)), np.empty((rows, Nt, Nt))
+        self._chk(self.lib.pilco_gp_predict_points_cov(self.h, slot, _ptr(Xs), Nt, int(output), _ptr(Za), _ptr(mean), _ptr(cov)))
+        return mean, cov
+
+    def gp_sample_points(self, slot, Xs, D, E, S, output=-1, Z_all=None, seed=0, draws=None, jitter=1e-6, parts=False):
+        """Joint samples of the latent functions at Xs (Nt, D): (S, Nt, E) = mean + chol(cov + jitter I) z per output (E = 1
+        for 0 <= output < E).  draws (S, Nt, E): the caller's standard normals; None: drawn on the device from `seed`
+        (Philox domain 5).  parts: also a dict(mean (E, Nt), cov, chol (E, Nt, Nt), draws (S, Nt, E)) of what the samples
+        were made from (include/pilco_hip.h: pilco_gp_sample_points)."""
+        rows = E if output < 0 else 1
+        Xs = _f64(Xs)
+        Nt, S = Xs.shape[0], int(S)
+        zi = None
+        if draws is not None:
+            zi = np.asarray(draws, np.float64)
+            if zi.shape != (S, Nt, rows):
+                raise ValueError(f"draws must be (S, Nt, E) = ({S}, {Nt}, {rows}), got {zi.shape}")
+            zi = _f64(zi)
+        Xs, Za = self._points_args(Xs, D, E, Z_all)
+        samples = np.empty((max(S, 0), Nt, rows))
+        mean = cov = chol = zo = None
+        if parts:
+            mean, cov, chol = np.empty((rows, Nt)), np.empty((rows, Nt, Nt)), np.empty((rows, Nt, Nt))
+            zo = np.empty((max(S, 0), Nt, rows))
+        self._chk(self.lib.pilco_gp_sample_points(self.h, slot, _ptr(Xs), Nt, int(output), _ptr(Za), S, int(seed) & (2 ** 64 - 1), _ptr(zi),
+                                                  float(jitter), _ptr(samples), _ptr(mean), _ptr(cov), _ptr(chol), _ptr(zo)))
+        if parts:
+            return samples, dict(mean=mean, cov=cov, chol=chol, draws=zo)
+        return samples
 
     # ---- policy / reward marshalling
     def _policy(self, spec):
@@ -894,6 +969,14 @@ class Context:
         ms = C.c_float()
         self._chk(self.lib.pilco_factorize_timed(self.h, slot, int(reps), C.byref(ms)))
         return ms.value
+
+    def predict_cov_timed(self, slot, Xs, reps):
+        """Developer measurement (-DPILCO_DEV builds; include/pilco_hip_dev.h): ms of k_predict_cov alone, ms of the same matrix
+        from launch_gram + launch_gemm + an add, and the largest difference of the two."""
+        Xs = _f64(Xs)
+        a, b, d = C.c_float(), C.c_float(), C.c_double()
+        self._chk(self.lib.pilco_debug_predict_cov_timed(self.h, slot, _ptr(Xs), Xs.shape[0], int(reps), C.byref(a), C.byref(b), C.byref(d)))
+        return a.value, b.value, d.value
 
     def set_pair_timing(self, on=True):
         self._chk(self.lib.pilco_set_pair_timing(self.h, 1 if on else 0))

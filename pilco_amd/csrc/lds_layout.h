@@ -247,6 +247,16 @@ PILCO_HD inline RevChainLds rev_chain_lds(int E, int U, int D) {
     return l;
 }
 
+// ------------------------------------------------------------------ the posterior covariance (predict_cov.hip: k_predict_cov)
+// static LDS, the same for every launch: the finished 64 x 64 tile turned around for its mirror image, the reciprocal lengthscales
+constexpr int PCOV_TILE = 64, PCOV_TP = 65;   // tile edge; pitch of the turned tile (odd: conflict-free both ways)
+struct PredictCovLds {
+    int tile;   // [PCOV_TILE][PCOV_TP]   element (b, a) of the tile (a, b)
+    int il;     // [32]   1 / l_d
+    int total;
+};
+PILCO_HD constexpr PredictCovLds predict_cov_lds() { return PredictCovLds{0, PCOV_TILE * PCOV_TP, PCOV_TILE * PCOV_TP + 32}; }
+
 // ------------------------------------------------------------------ what a launch asks for (doubles): the largest of its roles
 PILCO_HD inline int lds_launch_sweep(int npad, int njs, int kp, int D) { return lds_max(sweep_lds(sweep_jws(npad, njs), kp).total, head_lds(D).total); }
 PILCO_HD inline int lds_launch_bwd_post(int D) { return lds_max(pair_post_lds((D + 16) / 16).total, mean_partial_lds(D).total); }

@@ -8,7 +8,8 @@
 //   u1 = 1 - ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53  in (0, 1],   u2 = ((w2 >> 5) 2^26 + (w3 >> 6)) 2^-53  in [0, 1)
 //   r = sqrt(-2 ln u1),   z_2j = r cos(2 pi u2),   z_2j+1 = r sin(2 pi u2)
 // A draw depends on (seed, t, p, e) only: not on the particle count, not on how the particles are chunked.
-// The counter's fourth word is a domain: 0 above; 1..4 below, the function-sample rollout (particles_fn.hip).
+// The counter's fourth word is a domain: 0 above; 1..4 below, the function-sample rollout (particles_fn.hip); 5, the joint
+// posterior samples at test points (predict_cov.hip).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -66,7 +67,10 @@ PILCO_PHILOX_HD inline void philox_normal_pair(unsigned long long seed, uint32_t
 //   domain 2  {l, e, 0, 2}  u2: the phase b_el = 2 pi u2
 //   domain 3  {p, l, j, 3}  normals: the weights w_p,2j,l, w_p,2j+1,l of particle p (outputs 2j, 2j + 1, feature l)
 //   domain 4  {p, i, j, 4}  normals: the noise draws xi_p,2j,i, xi_p,2j+1,i (outputs 2j, 2j + 1, training point i)
-enum PhiloxDomain : uint32_t { PHILOX_STEP = 0u, PHILOX_FN_FREQ = 1u, PHILOX_FN_PHASE = 2u, PHILOX_FN_WEIGHT = 3u, PHILOX_FN_XI = 4u };
+//   domain 5  {s, a, j, 5}  normals: z_s,a,2j, z_s,a,2j+1 of pilco_gp_sample_points (sample s, test point a, outputs 2j, 2j + 1)
+enum PhiloxDomain : uint32_t {
+    PHILOX_STEP = 0u, PHILOX_FN_FREQ = 1u, PHILOX_FN_PHASE = 2u, PHILOX_FN_WEIGHT = 3u, PHILOX_FN_XI = 4u, PHILOX_COV_Z = 5u
+};
 
 PILCO_PHILOX_HD inline PhiloxWords philox_domain_words(unsigned long long seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t domain) {
     return philox4x32_10(c0, c1, c2, domain, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));

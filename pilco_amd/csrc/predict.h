@@ -16,6 +16,10 @@ struct PredictWork {
     DevBuf pt_ev_first, pt_ev_part, pt_ev_counts;
     DevBuf pg_A, pg_lam, pg_ds, pg_part, pg_rew, pg_out;
     DevBuf fn_om, fn_ph, fn_Wt, fn_phix, fn_R, fn_V, fn_xi, fn_raw;   // the function-sample rollout (particles_fn.hip)
+    // the full posterior covariance and the joint samples (predict_cov.hip): [Eu][Ntpad][Ntpad] covariance, its copy with
+    // the jitter (factored in place), the inverses of the factor's diagonal blocks; [Eu][Ntpad][Spad] normals and C z;
+    // [S][Nt][Eu] normals and samples in the caller's layout
+    DevBuf pc_cov, pc_fac, pc_linv, pc_z, pc_f, pc_zraw, pc_smp;
 };
 
 // The operator blocks and the points of the cross-covariance of Eu outputs of one model (device pointers).
@@ -40,5 +44,8 @@ int predict_points_device(pilco_ctx* ctx, const PredictModel& m, const double* X
 inline int predict_jac_nops(const PredictModel& m) { return m.iAt ? 2 : 1; }
 int predict_points_jac_device(pilco_ctx* ctx, const PredictModel& m, const double* Xt, int ntc, int ldt, const double* Ks,
                               double* W, double* dmean, double* dvar);
+// W alone, in the covariance's scaling (predict_cov.hip): W[0] = L^{-1} K*, FITC W[1] = sqrt(sn2) iAt K* -- the same walk
+// and the same product tiles as above, another factor on the second operator.  One launch; does not wait.
+int predict_points_w_device(pilco_ctx* ctx, const PredictModel& m, int ntc, int ldt, const double* Ks, double* W);
 // FITC operands of outputs e0 .. e0 + Eu - 1 on their own inducing inputs Z_all (host (E, M, D)), in pw.fitc
 int factorize_own_z(pilco_ctx* ctx, Slot& s, PredictWork& pw, const double* Z_all, int e0, int Eu);

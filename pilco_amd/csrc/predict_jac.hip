@@ -38,6 +38,7 @@ struct PredictJacArgs {
     double* dmean;        // [Eu][ldt][D]
     double* dvar;
     int n, npad, G, ntc, ldt, D;
+    int w_cov;            // k_predict_points_w: 0 the Jacobians' scaling above; 1 the covariance's (predict_cov.hip): the second operator's times sqrt(sn2)
 };
 
 // doubles of dynamic LDS: [4 waves][D][32 points] variance sums, [D][32] mean sums, [D] 1 / l_d^2
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void k_predict_points_w(PredictJacArgs a) {
                 }
         }
         // result register r of the lane: row 64 g + 16 rb + h + 4 r, point t0 + 16 ct + c
-        const double sc = op ? -a.noise[e] : 1.0;
+        const double sc = op ? (a.w_cov ? sqrt(a.noise[e]) : -a.noise[e]) : 1.0;
         double* Wt = a.W + (((long)op * gridDim.y + e) * a.ldt + t0 + c) * npad + 64 * g + h;
 #pragma unroll
         for (int rb = 0; rb < PJ_RB; ++rb)
@@ -280,6 +281,17 @@ int predict_points_jac_device(pilco_ctx* ctx, const PredictModel& m, const doubl
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_predict_points_jac, dim3(ldt / PJ_PTS, m.Eu), dim3(256), sizeof(double) * predict_jac_lds_doubles(m.D),
                        ctx->st, a);
+    HIPCHK(hipGetLastError());
+    return PILCO_OK;
+}
+
+int predict_points_w_device(pilco_ctx* ctx, const PredictModel& m, int ntc, int ldt, const double* Ks, double* W) {
+    PredictJacArgs a{};
+    a.Ks = Ks; a.sKs = (long)ldt * m.npad;
+    a.L = m.L; a.iAt = m.iAt; a.sL = (long)m.npad * m.npad; a.noise = m.sn2; a.W = W;
+    a.n = m.n; a.npad = m.npad; a.G = (m.n + 63) / 64; a.ntc = ntc; a.ldt = ldt; a.D = m.D;
+    a.w_cov = 1;
+    hipLaunchKernelGGL(k_predict_points_w, dim3(ldt / PJ_PTS, m.Eu), dim3(256), 0, ctx->st, a);
     HIPCHK(hipGetLastError());
     return PILCO_OK;
 }

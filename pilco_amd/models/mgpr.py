@@ -132,11 +132,63 @@ class MGPR:
                                                self.num_outputs, output, self._own_inducing())
         return tensor_value(mean.T), tensor_value(var.T)
 
-    def predict_f(self, Xnew, full_cov=False):
-        """Every output's GPR.predict_f at Xnew (Nt, D): mean and latent variance, (Nt, E) each (extension)."""
+    def _predict_points_cov(self, Xnew, output=-1):
+        """(mean (Nt, E), cov (E, Nt, Nt)) of the latent functions at Xnew (Nt, D); E = 1 for one output."""
+        self._user_factors = None
+        self._ensure_factorized()
+        mean, cov = self.ctx.gp_predict_points_cov(self._slot, np.asarray(Xnew, np.float64).reshape(-1, self.num_dims), self.num_dims,
+                                                   self.num_outputs, output, self._own_inducing())
+        return tensor_value(mean.T), tensor_value(cov)
+
+    def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
+        """Every output's GPR.predict_f at Xnew (Nt, D): mean and latent variance, (Nt, E) each (extension); full_cov=True:
+        the mean (Nt, E) and every output's posterior covariance between the test points, (E, Nt, Nt), GPflow's shapes
+        (pilco_gp_predict_points_cov, docs/predict_cov.md)."""
+        if full_output_cov:
+            raise NotImplementedError("predict_f: full_output_cov=True is not supported (the outputs are independent)")
         if full_cov:
-            raise NotImplementedError("predict_f: only full_cov=False (the marginal variances) is supported")
+            return self._predict_points_cov(Xnew)
         return self._predict_points(Xnew)
+
+    def _predict_f_samples(self, Xnew, output, num_samples, full_cov, full_output_cov, seed, draws, jitter, return_parts):
+        if full_output_cov:
+            raise NotImplementedError("predict_f_samples: full_output_cov=True is not supported (the outputs are independent)")
+        X = np.asarray(Xnew, np.float64).reshape(-1, self.num_dims)
+        S, Nt, rows = (1 if num_samples is None else int(num_samples)), X.shape[0], (self.num_outputs if output < 0 else 1)
+        if draws is not None:
+            draws = np.asarray(draws, np.float64)
+            if num_samples is None and draws.shape == (Nt, rows):
+                draws = draws[None]
+            if draws.shape != (S, Nt, rows):
+                raise ValueError("draws must be (num_samples, Nt, E) = (%d, %d, %d), got %s" % (S, Nt, rows, draws.shape))
+        if full_cov:
+            self._user_factors = None
+            self._ensure_factorized()
+            samples, parts = self.ctx.gp_sample_points(self._slot, X, self.num_dims, self.num_outputs, S, output, self._own_inducing(),
+                                                       seed=seed, draws=draws, jitter=jitter, parts=True)
+            parts = dict(mean=parts["mean"].T, cov=parts["cov"], chol=parts["chol"], draws=parts["draws"])
+        else:   # the marginals: mean + sqrt(var) z on predict_f's bits, the same stream of normals
+            from .._lib import philox_cov_normals
+            mean, var = (np.asarray(v) for v in self._predict_points(X, output))
+            if draws is None:
+                draws = philox_cov_normals(seed, S, Nt, range(self.num_outputs) if output < 0 else [output])
+            samples = mean[None] + np.sqrt(var)[None] * draws
+            parts = dict(mean=mean, var=var, cov=None, chol=None, draws=draws)
+        if num_samples is None:
+            samples, parts["draws"] = samples[0], parts["draws"][0]
+        if return_parts:
+            return tensor_value(samples), {k: (v if v is None else tensor_value(v)) for k, v in parts.items()}
+        return tensor_value(samples)
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, seed=0, draws=None, jitter=1e-6,
+                          return_parts=False):
+        """gpflow predict_f_samples for every output at Xnew (Nt, D): (S, Nt, E) joint samples of the latent functions,
+        mean + chol(cov + jitter I) z per output, or (Nt, E) for num_samples=None (pilco_gp_sample_points,
+        docs/predict_cov.md).  draws (S, Nt, E): the standard normals to use; None: drawn from `seed` (Philox domain 5; the same
+        seed gives the same samples).  full_cov=False: independent draws from the marginals, mean + sqrt(var) z with predict_f's
+        mean and variance.  return_parts=True: (samples, dict(mean (Nt, E), cov, chol (E, Nt, Nt), draws)); the draws fed
+        back as draws= reproduce the samples bit for bit."""
+        return self._predict_f_samples(Xnew, -1, num_samples, full_cov, full_output_cov, seed, draws, jitter, return_parts)
 
     def _predict_points_jac(self, Xnew, output=-1):
         """(mean, var, dmean, dvar) at Xnew (Nt, D): (Nt, E), (Nt, E) and (Nt, E, D) twice; E = 1 for one output."""

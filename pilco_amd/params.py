@@ -119,10 +119,25 @@ class GPModelView:
 
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """gpflow GPR.predict_f / GPRFITC.predict_f of this output at Xnew (Nt, D): latent mean and variance, (Nt, 1) each,
-        computed on the device (pilco_gp_predict_points)."""
+        computed on the device (pilco_gp_predict_points).  full_cov=True keeps raising here, as it always has on this view:
+        this output's covariance between the test points is predict_f_full_cov, every output's MGPR.predict_f(full_cov=True)."""
         if full_cov or full_output_cov:
-            raise NotImplementedError("predict_f: only full_cov=False, full_output_cov=False (the marginal variances) is supported")
+            raise NotImplementedError("predict_f: only full_cov=False, full_output_cov=False (the marginal variances) is supported; "
+                                      "predict_f_full_cov gives this output's covariance between the test points")
         return self._owner._predict_points(Xnew, self.index)
+
+    def predict_f_full_cov(self, Xnew):
+        """gpflow GPR.predict_f / GPRFITC.predict_f with full_cov=True of this output at Xnew (Nt, D): the mean (Nt, 1) and the
+        posterior covariance between the test points (1, Nt, Nt), GPflow's shapes (pilco_gp_predict_points_cov,
+        docs/predict_cov.md)."""
+        return self._owner._predict_points_cov(Xnew, self.index)
+
+    def predict_f_samples(self, Xnew, num_samples=None, full_cov=True, full_output_cov=False, seed=0, draws=None, jitter=1e-6,
+                          return_parts=False):
+        """gpflow predict_f_samples of this output at Xnew (Nt, D): (S, Nt, 1), or (Nt, 1) for num_samples=None.
+        See MGPR.predict_f_samples."""
+        return self._owner._predict_f_samples(Xnew, self.index, num_samples, full_cov, full_output_cov, seed, draws, jitter,
+                                              return_parts)
 
     def predict_f_jacobian(self, Xnew):
         """predict_f of this output with the derivatives with respect to the input (extension): (mean, var, dmean, dvar),
@@ -131,5 +146,7 @@ class GPModelView:
 
     def predict_y(self, Xnew, full_cov=False, full_output_cov=False):
         """gpflow's Gaussian-likelihood predict_y: predict_f with the likelihood variance added to the variance."""
+        if full_cov or full_output_cov:   # (as gpflow's Gaussian likelihood: predict_y has no full covariance)
+            raise NotImplementedError("predict_y: only full_cov=False, full_output_cov=False is supported")
         mean, var = self.predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
         return mean, tensor_value(np.asarray(var) + float(self.likelihood.variance.numpy()))
