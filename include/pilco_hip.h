@@ -332,6 +332,35 @@ int pilco_rollout_particles_fn_grad_rbf(pilco_ctx* ctx, const pilco_policy* poli
                                         const pilco_function_draws_out* draws_out, const double* Xp, const double* Yp,
                                         const double* lsp, const double* noisep, int bf, double* reward, double* reward_steps,
                                         double* dX, double* dY, double* dls, double* dreturn_dx0);
+/* Particle rollout CONDITIONED ON ITS OWN PATH (extension; docs/particle_conditioned.md): exact and consistent along a
+ * trajectory, for the exact GP and for FITC on the slot's shared inducing inputs.  The increments f(xt_0), .., f(xt_{H-1}) of a
+ * particle (xt = [x, u]) are jointly Gaussian under the posterior; step t is drawn conditioned on the particle's own earlier
+ * visited points.  Per particle and output e, with the rows w of pilco_gp_predict_points_cov:
+ *   c_ts = k_e(xt_t, xt_s) - w_t . w_s  (FITC: - w0_t . w0_s + w1_t . w1_s);   Lam Lam^T = C + jitter * variance_e * I by rows:
+ *   l_s = (c_ts - sum_{r<s} l_r Lam_sr) / Lam_ss,  d = c_tt + jitter * variance_e - sum_{s<t} l_s^2,  Lam_tt = sqrt(d)
+ *   x'_e = x_e + mu_t + sum_{s<t} l_s z_s + Lam_tt z_t  [+ sqrt(likelihood variance_e) zeta_t  with observation_noise]
+ * mu_t has the bits of pilco_gp_predict_points; z_s = eps[s][p][e] is the step stream of pilco_rollout_particles (the same seed
+ * gives the same first step up to the jitter); zeta is a second, independent stream (Philox domain 6, counter {p, t, j, 6}) and
+ * never enters the conditioning.  Every argument up to first_hit means what it means in pilco_rollout_particles_events.
+ * jitter: relative to the kernel variance, finite and >= 0 (1e-8 is the binding's default).  eps_obs (H,P,E), may be NULL: the
+ * caller's zeta, read only with observation_noise.  out (may be NULL, each member may be NULL): eps_obs (H,P,E), the zeta
+ * used, written only with observation_noise; path_cov and path_factor (P,E,H,H): c_ts (without jitter) and Lam in the lower
+ * triangle, zero above it.  A trajectory depends on its own x0 row and draws only: the same bits alone, in any batch or group.
+ * The call holds H nops E npad + E H (H+1) / 2 + H D + E npad + 2 E doubles per particle (nops: 1 exact, 2 FITC; the factor twice
+ * with path_cov) and runs in groups of a multiple of 64 particles within a budget of 2^29 doubles (the environment's
+ * PILCO_PARTICLE_COND_BUDGET, in doubles, read at every call); the statistics and events run after the last group over all
+ * particles, so grouping changes no bit.  Refuses, before any launch or upload and with nothing written, what
+ * pilco_rollout_particles_events refuses, H > PILCO_MAX_COND_STEPS, a jitter that is negative or not finite, nops * npad > 8192
+ * and a footprint over the budget for a group of 64 (the message names the largest H that fits).  PILCO_E_NOT_PD when a pivot
+ * d is not positive (NaN included): the message names particle, output and step (the earliest such step, there the lowest
+ * particle, then output), and nothing is written. */
+#define PILCO_MAX_COND_STEPS 128
+typedef struct pilco_cond_out { double *eps_obs, *path_cov, *path_factor; } pilco_cond_out;   /* each may be NULL */
+int pilco_rollout_particles_cond(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                 const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
+                                 double* mean, double* cov, double* reward_steps, double* particles, double* eps_out,
+                                 const pilco_event* events, int n_events, long long* counts, int* first_hit,
+                                 double jitter, const double* eps_obs, const pilco_cond_out* out);
 
 /* ------------------------------------------------------------------ reverse mode
  * The reference differentiates training_loss with TensorFlow's autodiff (pilco/models/pilco.py:85-90);

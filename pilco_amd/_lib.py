@@ -62,6 +62,13 @@ class FunctionDrawsOut(C.Structure):
     _fields_ = [("omega", _dp), ("phase", _dp), ("w", _dp), ("xi", _dp), ("v", _dp)]
 
 
+class CondOut(C.Structure):
+    _fields_ = [("eps_obs", _dp), ("path_cov", _dp), ("path_factor", _dp)]
+
+
+MAX_COND_STEPS = 128   # PILCO_MAX_COND_STEPS
+
+
 def event_spec_of(ev):
     """An event as the dict the binding takes: dict(clauses=[(dim, low, high), ...], complement=bool), a bound of None meaning
     no bound on that side.  ev: such a dict, or an object with event_spec() (pilco_amd.safe's constraints)."""
@@ -153,6 +160,10 @@ SIGNATURES = {
                                                       C.c_int, _dp, C.c_ulonglong, C.c_int, C.POINTER(FunctionDraws),
                                                       C.POINTER(FunctionDrawsOut), _dp, _dp, _dp, _dp, C.c_int,
                                                       _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles_cond": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                               _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp,
+                                               C.POINTER(Event), C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                               C.c_double, _dp, C.POINTER(CondOut)]),
     "pilco_gp_predict_vjp": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout_tape": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, _dp, C.c_int,
                                      _dp, _dp, _dp, _dp, _dp]),
@@ -669,6 +680,53 @@ class Context:
             first.ctypes.data_as(C.POINTER(C.c_int)) if events is not None else None,
             C.byref(d), C.byref(do) if do is not None else None))
         return mean, cov, rew, parts, used, counts, first, out
+
+    def rollout_particles_cond(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_particles=False,
+                               events=None, jitter=1e-8, eps_obs=None, want_path=False):
+        """P trajectories of H steps, each step drawn conditioned on the particle's own earlier visited points
+        (pilco_rollout_particles_cond; docs/particle_conditioned.md): exact GP or FITC.  eps (H, P, E): the step draws, or
+        None: generated on the device from ``seed``.  eps_obs (H, P, E): the observation-noise draws, read only with
+        observation_noise.  jitter: relative to the kernel variance.  Returns (mean, cov, reward_steps, particles or None,
+        eps used, counts or None, first_hit or None, eps_obs used or None, path_cov or None, path_factor or None); the last
+        two (P, E, H, H) with want_path."""
+        E = policy["state_dim"]
+        p, k1 = self._policy(policy)
+        r, k2 = self._rewards(rewards, E)
+        x0 = _f64(x0)
+        if x0.ndim != 2 or x0.shape[1] != E:
+            raise ValueError(f"initial particles must be (P, {E})")
+        P, H = x0.shape[0], int(H)
+        noisy = bool(observation_noise)
+        if eps is not None:
+            eps = _f64(eps)
+            if eps.shape != (H, P, E):
+                raise ValueError(f"draws must be ({H}, {P}, {E})")
+        if eps_obs is not None:
+            eps_obs = _f64(eps_obs)
+            if eps_obs.shape != (H, P, E):
+                raise ValueError(f"observation draws must be ({H}, {P}, {E})")
+        mean = np.empty((H + 1, E))
+        cov = np.empty((H + 1, E, E))
+        rew = np.empty((max(H, 0),))
+        parts = np.empty((H + 1, P, E)) if want_particles else None
+        used = np.empty((H, P, E))
+        Hc = min(max(H, 0), MAX_COND_STEPS)   # (a longer horizon is refused by the library: no array of its size here)
+        zeta = np.empty((H, P, E)) if noisy else None
+        pcov = np.zeros((P, E, Hc, Hc)) if want_path else None
+        pfac = np.zeros((P, E, Hc, Hc)) if want_path else None
+        co = CondOut(_ptr(zeta), _ptr(pcov), _ptr(pfac))
+        events = list(events) if events is not None else None
+        K = len(events) if events is not None else 0
+        ev = self._events(events) if events is not None else None
+        counts = np.zeros((H + 1, K), np.int64) if events is not None else None
+        first = np.full((P, K), -1, np.int32) if events is not None else None
+        self._chk(self.lib.pilco_rollout_particles_cond(
+            self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            1 if noisy else 0, _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used), ev, K,
+            counts.ctypes.data_as(C.POINTER(C.c_longlong)) if events is not None else None,
+            first.ctypes.data_as(C.POINTER(C.c_int)) if events is not None else None,
+            C.c_double(float(jitter)), _ptr(eps_obs) if noisy else None, C.byref(co)))
+        return mean, cov, rew, parts, used, counts, first, zeta, pcov, pfac
 
     def _particle_grad_args(self, policy, rewards, x0, H, eps, seed, observation_noise):
         E = policy["state_dim"]

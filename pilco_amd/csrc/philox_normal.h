@@ -9,7 +9,8 @@
 //   r = sqrt(-2 ln u1),   z_2j = r cos(2 pi u2),   z_2j+1 = r sin(2 pi u2)
 // A draw depends on (seed, t, p, e) only: not on the particle count, not on how the particles are chunked.
 // The counter's fourth word is a domain: 0 above; 1..4 below, the function-sample rollout (particles_fn.hip); 5, the joint
-// posterior samples at test points (predict_cov.hip).
+// posterior samples at test points (predict_cov.hip); 6, the observation noise of the path-conditioned rollout
+// (particles_cond.hip).
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -68,8 +69,10 @@ PILCO_PHILOX_HD inline void philox_normal_pair(unsigned long long seed, uint32_t
 //   domain 3  {p, l, j, 3}  normals: the weights w_p,2j,l, w_p,2j+1,l of particle p (outputs 2j, 2j + 1, feature l)
 //   domain 4  {p, i, j, 4}  normals: the noise draws xi_p,2j,i, xi_p,2j+1,i (outputs 2j, 2j + 1, training point i)
 //   domain 5  {s, a, j, 5}  normals: z_s,a,2j, z_s,a,2j+1 of pilco_gp_sample_points (sample s, test point a, outputs 2j, 2j + 1)
+//   domain 6  {p, t, j, 6}  normals: zeta_t,p,2j, zeta_t,p,2j+1, the observation noise of pilco_rollout_particles_cond
 enum PhiloxDomain : uint32_t {
-    PHILOX_STEP = 0u, PHILOX_FN_FREQ = 1u, PHILOX_FN_PHASE = 2u, PHILOX_FN_WEIGHT = 3u, PHILOX_FN_XI = 4u, PHILOX_COV_Z = 5u
+    PHILOX_STEP = 0u, PHILOX_FN_FREQ = 1u, PHILOX_FN_PHASE = 2u, PHILOX_FN_WEIGHT = 3u, PHILOX_FN_XI = 4u, PHILOX_COV_Z = 5u,
+    PHILOX_COND_OBS = 6u
 };
 
 PILCO_PHILOX_HD inline PhiloxWords philox_domain_words(unsigned long long seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t domain) {

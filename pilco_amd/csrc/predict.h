@@ -20,6 +20,10 @@ struct PredictWork {
     // the jitter (factored in place), the inverses of the factor's diagonal blocks; [Eu][Ntpad][Spad] normals and C z;
     // [S][Nt][Eu] normals and samples in the caller's layout
     DevBuf pc_cov, pc_fac, pc_linv, pc_z, pc_f, pc_zraw, pc_smp;
+    // the path-conditioned particle rollout (particles_cond.hip): the histories of W rows [H][nops][E][G][npad] and of points
+    // [H][D][G], the packed factor and path covariance [G][E][H (H + 1) / 2], the observation draws [H][P][E], the rewards
+    // [H][P], the pivot words [G][E] (int)
+    DevBuf pc2_Wh, pc2_Xh, pc2_lam, pc2_cov, pc2_zeta, pc2_rew, pc2_info;
 };
 
 // The operator blocks and the points of the cross-covariance of Eu outputs of one model (device pointers).

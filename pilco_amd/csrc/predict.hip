@@ -153,7 +153,8 @@ void predict_release(Slot& s) {
     for (DevBuf* b : {&p.raw, &p.Xt, &p.Ks, &p.out, &p.jac, &p.jacW, &p.pt_x, &p.pt_eps, &p.pt_rew, &p.pt_part, &p.pt_stats, &p.pt_par,
                       &p.pt_ev_first, &p.pt_ev_part, &p.pt_ev_counts, &p.pg_A, &p.pg_lam, &p.pg_ds, &p.pg_part, &p.pg_rew, &p.pg_out,
                       &p.fn_om, &p.fn_ph, &p.fn_Wt, &p.fn_phix, &p.fn_R, &p.fn_V, &p.fn_xi, &p.fn_raw,
-                      &p.pc_cov, &p.pc_fac, &p.pc_linv, &p.pc_z, &p.pc_f, &p.pc_zraw, &p.pc_smp})
+                      &p.pc_cov, &p.pc_fac, &p.pc_linv, &p.pc_z, &p.pc_f, &p.pc_zraw, &p.pc_smp,
+                      &p.pc2_Wh, &p.pc2_Xh, &p.pc2_lam, &p.pc2_cov, &p.pc2_zeta, &p.pc2_rew, &p.pc2_info})
         b->release();
     Slot& f = p.fitc;
     for (ChainGraph* cg : {&f.g_fact, &f.g_fitc, &f.g_fitc_nlml}) chain_graph_release(*cg);

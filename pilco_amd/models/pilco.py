@@ -20,11 +20,15 @@ class ParticleTrajectories:
     number of particles that hit event k at state t; event_prob = event_counts / P; first_hit (P, K), the first such t of
     every particle or -1.  None without events.  function_draws: with dynamics="function" and return_particles=True the
     dict of omega (E, L, D), phase (E, L), w (P, E, L), xi (P, E, N), v (P, E, N) the call used (docs/particle_functions.md);
-    else None."""
+    else None.  eps_obs (n, P, E), path_cov and path_factor (P, E, n, n): with dynamics="conditioned" and
+    return_particles=True the observation-noise draws used (None without observation_noise), the path covariance c_ts and
+    its factor, lower triangles (docs/particle_conditioned.md); else None."""
 
-    def __init__(self, mean, cov, reward_steps, particles, eps, event_counts=None, first_hit=None, function_draws=None):
+    def __init__(self, mean, cov, reward_steps, particles, eps, event_counts=None, first_hit=None, function_draws=None, *,
+                 eps_obs=None, path_cov=None, path_factor=None):
         self.mean, self.cov, self.reward_steps, self.particles, self.eps = mean, cov, reward_steps, particles, eps
         self.function_draws = function_draws
+        self.eps_obs, self.path_cov, self.path_factor = eps_obs, path_cov, path_factor
         self.reward = np.asarray(reward_steps, np.float64).sum().reshape(1, 1)
         self.event_counts, self.first_hit = event_counts, first_hit
         self.event_prob = None if event_counts is None else event_counts / float(first_hit.shape[0])
@@ -205,10 +209,14 @@ class PILCO:
         root = (V * np.sqrt(np.clip(w, 0.0, None))) @ V.T
         return m + np.random.default_rng(seed).standard_normal((int(num_particles), E)) @ root
 
-    def _check_particle_dynamics(self, who, dynamics):
-        """the dynamics argument of the particle methods, before any device call"""
-        if dynamics not in ("marginal", "function"):
-            raise ValueError("%s: dynamics must be 'marginal' or 'function', got %r" % (who, dynamics))
+    def _check_particle_dynamics(self, who, dynamics, conditioned=False):
+        """the dynamics argument of the particle methods, before any device call; conditioned: the method has the
+        path-conditioned rollout (sample_trajectories; its gradient does not exist)"""
+        if dynamics not in ("marginal", "function", "conditioned"):
+            raise ValueError("%s: dynamics must be 'marginal', 'function' or 'conditioned', got %r" % (who, dynamics))
+        if dynamics == "conditioned" and not conditioned:
+            raise NotImplementedError("%s: dynamics='conditioned' has no gradient; the path-conditioned rollout is "
+                                      "sample_trajectories' (docs/particle_conditioned.md)" % who)
         if dynamics == "function" and isinstance(self.mgpr, SMGPR):
             raise NotImplementedError("%s: dynamics='function' needs an exact GP (MGPR); function samples of a "
                                       "sparse model are not supported" % who)
@@ -323,7 +331,8 @@ class PILCO:
         return M, S, R, traj
 
     def sample_trajectories(self, m_x, s_x, n, num_particles=1000, seed=0, eps=None, x0=None, observation_noise=False,
-                            return_particles=False, events=None, dynamics="marginal", num_features=512, function_draws=None):
+                            return_particles=False, events=None, dynamics="marginal", num_features=512, function_draws=None,
+                            jitter=1e-8, eps_obs=None):
         """Extension: num_particles trajectories of n steps sampled through the learned dynamics on the device
         (pilco_rollout_particles), to hold against the Gaussians predict() propagates.  Every particle acts with
         compute_action(x) and moves by a draw from the GP posterior at [x, u] (latent variance; observation_noise adds the
@@ -341,8 +350,19 @@ class PILCO:
         features conditioned on the data pathwise, or the caller's function_draws (the result's function_draws fed back
         reproduces every output bitwise) -- and follows it deterministically (pilco_rollout_particles_fn,
         docs/particle_functions.md); eps is then used only with observation_noise (the result's eps is None without it).
-        Exact GP only: an SMGPR raises NotImplementedError.  Any other value raises ValueError."""
-        self._check_particle_dynamics("sample_trajectories", dynamics)
+        Exact GP only: an SMGPR raises NotImplementedError.
+        dynamics="conditioned": every step is drawn conditioned on the particle's own earlier visited points -- the exact
+        joint posterior along the trajectory, for MGPR and SMGPR alike (pilco_rollout_particles_cond,
+        docs/particle_conditioned.md).  eps is the step stream of "marginal" (the same seed gives the same first step up to
+        the jitter); observation noise is a second stream, eps_obs (n, P, E) or generated, which never enters the
+        conditioning.  jitter (relative to the kernel variance) is added to the path covariance before it is factored.  With
+        return_particles the result carries eps_obs, path_cov and path_factor.  n is at most 128.  num_features (other than
+        its default) and function_draws raise ValueError here.  Any other value of dynamics raises ValueError."""
+        self._check_particle_dynamics("sample_trajectories", dynamics, conditioned=True)
+        if dynamics == "conditioned" and (num_features != 512 or function_draws is not None):
+            raise ValueError("sample_trajectories: num_features and function_draws belong to dynamics='function', not 'conditioned'")
+        if dynamics != "conditioned" and eps_obs is not None:
+            raise ValueError("sample_trajectories: eps_obs belongs to dynamics='conditioned'")
         host = self._host_reward_terms()
         if any(not hasattr(r, "event_spec") for _, r in host):
             raise NotImplementedError("sample_trajectories: reward terms evaluated on the host are not supported on particles; "
@@ -358,6 +378,20 @@ class PILCO:
         if dynamics == "function":
             return self._sample_function_trajectories(x0, int(n), eps, seed, observation_noise, return_particles, events, K, table,
                                                       host, num_features, function_draws)
+        if dynamics == "conditioned":
+            mean, cov, rew, parts, used, counts, first, zeta, pcov, pfac = self.ctx.rollout_particles_cond(
+                self._policy_spec(), self._reward_terms(), x0, int(n), eps=eps, seed=seed, observation_noise=observation_noise,
+                want_particles=return_particles, events=table if (events is not None or host) else None, jitter=jitter,
+                eps_obs=eps_obs, want_path=return_particles)
+            if host:   # the mean over the particles of c * 1[hit] at the pre-step states
+                for j, (c, _) in enumerate(host):
+                    for t in range(int(n)):
+                        rew[t] += c * float(counts[t, K + j]) / x0.shape[0]
+            kw = dict(eps_obs=zeta if return_particles else None, path_cov=pcov, path_factor=pfac)
+            if events is None:
+                return ParticleTrajectories(mean, cov, rew, parts, used, **kw)
+            return ParticleTrajectories(mean, cov, rew, parts, used, np.ascontiguousarray(counts[:, :K]),
+                                        np.ascontiguousarray(first[:, :K]), **kw)
         out = self.ctx.rollout_particles(self._policy_spec(), self._reward_terms(), x0, int(n), eps=eps, seed=seed,
                                          observation_noise=observation_noise, want_particles=return_particles,
                                          events=table if (events is not None or host) else None)

@@ -158,14 +158,16 @@ class SafePILCO(PILCO):
     def sample_risk(self, m_x, s_x, n, num_particles=1000, seed=0, dynamics="marginal", num_features=512, **kwargs):
         """Extension: the risk predict() scores a policy with, beside the learned model's own answer on particles
         (sample_trajectories with reward_mult's event; docs/particles.md).  kwargs go to sample_trajectories (eps, x0,
-        observation_noise, return_particles); dynamics ("marginal" or "function") and num_features are sample_trajectories'
-        own (docs/particle_functions.md).  Returns a RiskSample.  risk_moment_matched follows the reference (the variance
-        entry as the Normal scale, the steps independent in any_hit_moment_matched): it need not agree with the particles."""
+        observation_noise, return_particles, jitter, eps_obs); dynamics ("marginal", "function" or "conditioned") and
+        num_features are sample_trajectories' own (docs/particle_functions.md, docs/particle_conditioned.md).  Returns a
+        RiskSample.  risk_moment_matched follows the reference (the variance entry as the Normal scale, the steps independent in any_hit_moment_matched): it need not agree with the particles."""
         if not hasattr(self.reward_mult, "event_spec"):
             raise TypeError("sample_risk: reward_mult offers no event_spec()")
         n, E = int(n), self.state_dim
+        if dynamics != "conditioned" or num_features != 512:   # (the conditioned rollout has no features: it refuses them)
+            kwargs["num_features"] = num_features
         res = self.sample_trajectories(m_x, s_x, n, num_particles=num_particles, seed=seed, events=[self.reward_mult], dynamics=dynamics,
-                                       num_features=num_features, **kwargs)
+                                       **kwargs)
         traj = self.predict_trajectory(m_x, s_x, n)[3]
         risk_mm = np.array([float(np.ravel(self.reward_mult.compute_reward(traj[t, :E].reshape(1, E), traj[t, E:].reshape(E, E))[0])[0])
                             for t in range(n)], np.float64).reshape(n)
