@@ -584,35 +584,12 @@ class Context:
         events (a list of K event dicts, see event_spec_of; pilco_rollout_particles_events): two more results follow, counts
         (H+1, K) int64 -- the number of particles that hit event k at state t -- and first_hit (P, K) int32, the first such
         t of every particle or -1."""
-        E = policy["state_dim"]
-        p, k1 = self._policy(policy)
-        r, k2 = self._rewards(rewards, E)
-        x0 = _f64(x0)
-        if x0.ndim != 2 or x0.shape[1] != E:
-            raise ValueError(f"initial particles must be (P, {E})")
-        P, H = x0.shape[0], int(H)
-        if eps is not None:
-            eps = _f64(eps)
-            if eps.shape != (H, P, E):
-                raise ValueError(f"draws must be ({H}, {P}, {E})")
-        mean = np.empty((H + 1, E))
-        cov = np.empty((H + 1, E, E))
-        rew = np.empty((max(H, 0),))
-        parts = np.empty((H + 1, P, E)) if want_particles else None
-        used = np.empty((H, P, E))
-        args = (self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                1 if observation_noise else 0, _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used))
+        head, tail, res, keep = self._particle_forward_args(policy, rewards, x0, H, eps, seed, observation_noise, want_particles, events)
         if events is None:
-            self._chk(self.lib.pilco_rollout_particles(*args))
-            return mean, cov, rew, parts, used
-        events = list(events)
-        K = len(events)
-        ev = self._events(events)
-        counts = np.zeros((H + 1, K), np.int64)
-        first = np.full((P, K), -1, np.int32)
-        self._chk(self.lib.pilco_rollout_particles_events(*args, ev, K, counts.ctypes.data_as(C.POINTER(C.c_longlong)),
-                                                          first.ctypes.data_as(C.POINTER(C.c_int))))
-        return mean, cov, rew, parts, used, counts, first
+            self._chk(self.lib.pilco_rollout_particles(*head))
+            return res[:5]
+        self._chk(self.lib.pilco_rollout_particles_events(*head, *tail))
+        return res
 
     def _function_draws(self, policy, P, num_features, function_draws, want_draws):
         """function_draws (None: num_features of them, generated) -> the pilco_function_draws of a call, its
@@ -650,36 +627,11 @@ class Context:
         w (P, E, L), xi (P, E, N), which sets L.  eps (H, P, E) is read, and the draws used are returned, only with
         observation_noise (else the fifth result is None).  Returns (mean, cov, reward_steps, particles or None, eps used or
         None, counts or None, first_hit or None, draws or None); draws (want_draws): the dict above plus v (P, E, N)."""
-        E = policy["state_dim"]
-        p, k1 = self._policy(policy)
-        r, k2 = self._rewards(rewards, E)
-        x0 = _f64(x0)
-        if x0.ndim != 2 or x0.shape[1] != E:
-            raise ValueError(f"initial particles must be (P, {E})")
-        P, H = x0.shape[0], int(H)
-        noisy = bool(observation_noise)
-        if eps is not None:
-            eps = _f64(eps)
-            if eps.shape != (H, P, E):
-                raise ValueError(f"draws must be ({H}, {P}, {E})")
-        d, do, out, keep = self._function_draws(policy, P, num_features, function_draws, want_draws)
-        mean = np.empty((H + 1, E))
-        cov = np.empty((H + 1, E, E))
-        rew = np.empty((max(H, 0),))
-        parts = np.empty((H + 1, P, E)) if want_particles else None
-        used = np.empty((H, P, E)) if noisy else None
-        events = list(events) if events is not None else None
-        K = len(events) if events is not None else 0
-        ev = self._events(events) if events is not None else None
-        counts = np.zeros((H + 1, K), np.int64) if events is not None else None
-        first = np.full((P, K), -1, np.int32) if events is not None else None
-        self._chk(self.lib.pilco_rollout_particles_fn(
-            self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            1 if noisy else 0, _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used), ev, K,
-            counts.ctypes.data_as(C.POINTER(C.c_longlong)) if events is not None else None,
-            first.ctypes.data_as(C.POINTER(C.c_int)) if events is not None else None,
-            C.byref(d), C.byref(do) if do is not None else None))
-        return mean, cov, rew, parts, used, counts, first, out
+        head, tail, res, keep = self._particle_forward_args(policy, rewards, x0, H, eps, seed, observation_noise, want_particles, events,
+                                                            want_used=bool(observation_noise))
+        d, do, out, keep2 = self._function_draws(policy, head[5], num_features, function_draws, want_draws)
+        self._chk(self.lib.pilco_rollout_particles_fn(*head, *tail, C.byref(d), C.byref(do) if do is not None else None))
+        return res + (out,)
 
     def rollout_particles_cond(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_particles=False,
                                events=None, jitter=1e-8, eps_obs=None, want_path=False):
@@ -689,44 +641,20 @@ class Context:
         observation_noise.  jitter: relative to the kernel variance.  Returns (mean, cov, reward_steps, particles or None,
         eps used, counts or None, first_hit or None, eps_obs used or None, path_cov or None, path_factor or None); the last
         two (P, E, H, H) with want_path."""
-        E = policy["state_dim"]
-        p, k1 = self._policy(policy)
-        r, k2 = self._rewards(rewards, E)
-        x0 = _f64(x0)
-        if x0.ndim != 2 or x0.shape[1] != E:
-            raise ValueError(f"initial particles must be (P, {E})")
-        P, H = x0.shape[0], int(H)
-        noisy = bool(observation_noise)
-        if eps is not None:
-            eps = _f64(eps)
-            if eps.shape != (H, P, E):
-                raise ValueError(f"draws must be ({H}, {P}, {E})")
+        head, tail, res, keep = self._particle_forward_args(policy, rewards, x0, H, eps, seed, observation_noise, want_particles, events)
+        E, P, H, noisy = policy["state_dim"], head[5], head[6], bool(observation_noise)
         if eps_obs is not None:
             eps_obs = _f64(eps_obs)
             if eps_obs.shape != (H, P, E):
                 raise ValueError(f"observation draws must be ({H}, {P}, {E})")
-        mean = np.empty((H + 1, E))
-        cov = np.empty((H + 1, E, E))
-        rew = np.empty((max(H, 0),))
-        parts = np.empty((H + 1, P, E)) if want_particles else None
-        used = np.empty((H, P, E))
         Hc = min(max(H, 0), MAX_COND_STEPS)   # (a longer horizon is refused by the library: no array of its size here)
         zeta = np.empty((H, P, E)) if noisy else None
         pcov = np.zeros((P, E, Hc, Hc)) if want_path else None
         pfac = np.zeros((P, E, Hc, Hc)) if want_path else None
         co = CondOut(_ptr(zeta), _ptr(pcov), _ptr(pfac))
-        events = list(events) if events is not None else None
-        K = len(events) if events is not None else 0
-        ev = self._events(events) if events is not None else None
-        counts = np.zeros((H + 1, K), np.int64) if events is not None else None
-        first = np.full((P, K), -1, np.int32) if events is not None else None
-        self._chk(self.lib.pilco_rollout_particles_cond(
-            self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
-            1 if noisy else 0, _ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used), ev, K,
-            counts.ctypes.data_as(C.POINTER(C.c_longlong)) if events is not None else None,
-            first.ctypes.data_as(C.POINTER(C.c_int)) if events is not None else None,
-            C.c_double(float(jitter)), _ptr(eps_obs) if noisy else None, C.byref(co)))
-        return mean, cov, rew, parts, used, counts, first, zeta, pcov, pfac
+        self._chk(self.lib.pilco_rollout_particles_cond(*head, *tail, C.c_double(float(jitter)), _ptr(eps_obs) if noisy else None,
+                                                        C.byref(co)))
+        return res + (zeta, pcov, pfac)
 
     def _particle_grad_args(self, policy, rewards, x0, H, eps, seed, observation_noise):
         E = policy["state_dim"]
@@ -743,6 +671,30 @@ class Context:
         head = (self.h, C.byref(p), r, len(rewards), _ptr(x0), P, H, _ptr(eps), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF),
                 1 if observation_noise else 0)
         return head, (p, k1, r, k2, x0, eps), P, H
+
+    def _particle_forward_args(self, policy, rewards, x0, H, eps, seed, observation_noise, want_particles, events, want_used=True):
+        """What the three forward particle calls share: the checks of x0 and eps, the leading arguments of
+        pilco_rollout_particles (head), the event arguments of the other entry points (tail), the result arrays (mean, cov,
+        reward_steps, particles or None, draws used or None, counts or None, first_hit or None) and what to keep alive."""
+        E = policy["state_dim"]
+        head, keep, P, H = self._particle_grad_args(policy, rewards, x0, H, eps, seed, observation_noise)
+        mean = np.empty((H + 1, E))
+        cov = np.empty((H + 1, E, E))
+        rew = np.empty((max(H, 0),))
+        parts = np.empty((H + 1, P, E)) if want_particles else None
+        used = np.empty((H, P, E)) if want_used else None
+        ev = counts = first = None
+        K = 0
+        if events is not None:
+            events = list(events)
+            K = len(events)
+            ev = self._events(events)
+            counts = np.zeros((H + 1, K), np.int64)
+            first = np.full((P, K), -1, np.int32)
+        tail = (ev, K, counts.ctypes.data_as(C.POINTER(C.c_longlong)) if events is not None else None,
+                first.ctypes.data_as(C.POINTER(C.c_int)) if events is not None else None)
+        return (head + (_ptr(mean), _ptr(cov), _ptr(rew), _ptr(parts), _ptr(used)), tail, (mean, cov, rew, parts, used, counts, first),
+                (keep, ev))
 
     def rollout_particles_grad(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_dx0=False):
         """Value and pathwise gradient of the particle return J = reward_steps.sum() of rollout_particles on the same x0 and

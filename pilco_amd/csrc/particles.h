@@ -1,10 +1,13 @@
-// What the particle rollout (particles.hip) shares with its gradient (particles_grad.hip) and with the function-sample
-// rollout (particles_fn.hip): the arguments of the action, draw, statistics and event kernels, their launches, the reward
-// terms at a point, and the policy / reward checks and staging.  The kernels themselves live in particles.hip.  Below them:
-// the arguments and launches of the gradient's reverse sweep (kernels in particles_grad.hip), which the function-sample
-// gradient (particles_fn_grad.hip) runs on its own step matrices.
+// What the particle entry points share.  Device side: the arguments of the action, draw, statistics and event kernels
+// (kernels in particles.hip), the reward terms at a point, and the arguments of the gradient's reverse sweep (kernels in
+// particles_grad.hip; the function-sample gradient runs it on its own step matrices), each with its launch.  Host side
+// (particle_frame.hip, docs/particle_frame.md): the checks and the staging of policy and rewards, ParticleFrame -- what the
+// three forward rollouts do around their step loops -- and ParticleGradFrame -- what the two gradients do around their
+// forward passes.
 #pragma once
 #include "predict.h"
+
+#include <functional>
 
 namespace pilco {
 
@@ -133,7 +136,7 @@ struct StreamDrain {   // the staging vectors of a call are locals: nothing of t
 void launch_particle_head(hipStream_t st, const pilco::ParticleHeadArgs& a);
 void launch_particle_tail(hipStream_t st, const pilco::ParticleTailArgs& a);
 // the statistics of one state over all particles (k_particle_partials, k_particle_finish) and its events (k_particle_events,
-// k_particle_events_finish): the launches of pilco_rollout_particles, shared with the function-sample rollout (particles_fn.hip)
+// k_particle_events_finish): ParticleFrame::state launches them for every forward rollout
 void launch_particle_stats(hipStream_t st, const pilco::ParticleStatArgs& a);
 void launch_particle_events(hipStream_t st, const pilco::ParticleEventArgs& a);
 // what pilco_rollout_particles refuses about the slot, the context, P and H; about the policy and the reward terms (in this
@@ -150,3 +153,109 @@ void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double
 // the reward terms into hp (from off on) and rw[0 .. n_rewards - 1]
 void stage_rewards(const pilco_reward_term* rewards, int n_rewards, int E, std::vector<double>& hp, size_t& off, const double* dev,
                    pilco::ParticleReward* rw);
+
+// ---- the forward frame.  Call order of a driver: check, its own refusals, open, its own buffers, upload, state(0, nullptr),
+// its steps with state(t + 1, rew) behind each (or every state after the last step), download, download_events, its own
+// downloads, the synchronisation, its host copies, finish.
+
+struct ParticleCall {   // the arguments the forward entry points share
+    const pilco_policy* policy;
+    const pilco_reward_term* rewards;
+    int n_rewards;
+    const double* x0;
+    int P, H;
+    const double* eps;
+    unsigned long long seed;
+    int observation_noise;
+    double *mean, *cov, *reward_steps, *particles, *eps_out;
+    const pilco_event* events;
+    int n_events;
+    long long* counts;
+    int* first_hit;
+};
+
+// hipSetDevice, the factorisation if it is stale, the dynamics slot's PredictWork (created on first use)
+int particle_work(pilco_ctx* ctx, PredictWork*& work);
+
+struct ParticleFrame {
+    pilco_ctx* ctx;
+    const ParticleCall c;
+    PredictWork* work = nullptr;   // set by open; from then on the destructor drains the stream (hp and hstats are its staging)
+    hipStream_t st = nullptr;
+    int E = 0, D = 0, U = 0, Q = 0, K = 0, nblk = 0, nslab = 0;   // Q = E + E*E + 1 statistics per state, K events
+    size_t PE = 0, eps_doubles = 0, fh_bytes = 0;
+    std::vector<double> hp, hstats;   // parameters (particle_par_doubles), statistics [H+1][Q]
+    pilco::ParticleHeadArgs ha{};     // the staged policy
+    pilco::ParticleStatArgs sa{};
+    pilco::ParticleEventArgs ea{};
+    ~ParticleFrame() { if (work) (void)hipStreamSynchronize(st); }
+    // the refusals every entry makes first, before any device call; who: the entry point without "pilco_"
+    int check(const char* who);
+    // device, factorisation, PredictWork; pt_x [nslab][P][E], pt_eps [eps_doubles] (0: none), pt_part, pt_stats, pt_par, pt_ev_*;
+    // policy and rewards staged into hp (rw: the step kernel's reward terms); the statistics' and events' arguments
+    int open(int nslab, size_t eps_doubles, pilco::ParticleReward* rw);
+    // one upload: parameters, initial particles, the caller's draws (where pt_eps is kept)
+    int upload();
+    double* slab(int t) const { return work->pt_x.p + (size_t)(nslab > c.H ? t : (t & 1)) * PE; }
+    // moments and events of the states after t steps; rew [P]: the rewards of step t - 1, nullptr for t = 0 (which first sets
+    // every first hit to -1)
+    int state(int t, const double* rew);
+    // the copies back, enqueued: statistics into hstats, pt_x into particles, pt_eps into eps_out (nullptr: not wanted);
+    // the events' counts and first hits
+    int download(double* particles, double* eps_out);
+    int download_events(long long* counts, int* first_hit);
+    // after the synchronisation: hstats into the caller's mean, cov and reward_steps
+    void finish();
+};
+
+// ---- the gradient frame.  Call order: (attach,) open, the forward's own buffers, upload, its set-up, sweep, finish_enqueue,
+// the driver's own downloads, the synchronisation, finish.
+
+struct PgPlan {   // groups of Pg particles (a multiple of PT_BLOCK, or all P), ldg columns of stored matrices, per_particle doubles each
+    size_t per_particle;
+    int Pg, ldg, nblk;
+};
+PgPlan pg_plan(int P, int H, int E, int D, size_t budget);
+
+struct ParticleGradFrame {
+    pilco_ctx* ctx;
+    const pilco_policy* policy;
+    const pilco_reward_term* rewards;
+    int n_rewards;
+    const double* x0;
+    int P, H;
+    double* dreturn_dx0;
+    int E, D, U, Q;   // Q: pg_quantities of the policy (0 without controls)
+    size_t PE;
+    PredictWork* work = nullptr;   // as ParticleFrame
+    hipStream_t st = nullptr;
+    PgPlan pl{};
+    std::vector<double> hp, hout, hlam;   // parameters, [H] rewards | [Q] parameter sums, lam_0 of a group [E][ldg]
+    pilco::PgReverseArgs ra{};
+    pilco::PgParamArgs pa{};
+    pilco::ParticleHeadArgs ha{};   // the staged policy, for the forward
+    // the dimensions; par: sized to Q and zeroed.  Touches no device
+    ParticleGradFrame(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0, int P,
+                      int H, double* dreturn_dx0, std::vector<double>& par);
+    ~ParticleGradFrame() { if (work) (void)hipStreamSynchronize(st); }
+    int attach() { st = ctx->st; return particle_work(ctx, work); }
+    // H > 0.  The plan, the pt_* and pg_* buffers (pt_eps: eps_doubles, 0: none), policy and rewards staged (rw: the forward
+    // kernel's reward terms); one upload: parameters, initial particles, the draws (nullptr: none), the parameter cells zeroed
+    int open(size_t eps_doubles, pilco::ParticleReward* rw);
+    int upload(const double* eps);
+    double* slab(int t) const { return work->pt_x.p + (size_t)t * PE; }
+    // per group: step(g0, ng, t), t = 0 .. H-1 -- the forward launches of the group's ng particles from g0 -- each followed
+    // by its reward sums; the reverse sweep t = H-1 .. 0; lam_0 into dreturn_dx0
+    int sweep(const std::function<int(int g0, int ng, int t)>& step);
+    // the blocks' cells in block order and their download, enqueued; after the synchronisation: J in step order, par
+    int finish_enqueue();
+    void finish(double* reward, double* reward_steps, std::vector<double>& par);
+};
+
+// what the four gradient entry points do around their rollout (which fills par); who: the entry point without "pilco_" and
+// "_rbf".  LinearController or none: the refusal of null dW, db and par = dW | db.  RbfController: the refusals, the
+// singularity probe, and dbeta | dC | dl through beta_k = (K_k + noise_k I)^-1 Y_k into dX, dY and dls
+using PgRollout = std::function<int(std::vector<double>& par)>;
+int pg_linear_entry(pilco_ctx* ctx, const char* who, const pilco_policy* policy, double* dW, double* db, const PgRollout& rollout);
+int pg_rbf_entry(pilco_ctx* ctx, const char* who, const pilco_policy* policy, const double* Xp, const double* Yp, const double* lsp,
+                 const double* noisep, int bf, double* dX, double* dY, double* dls, const PgRollout& rollout);

@@ -185,184 +185,37 @@ void launch_particle_events(hipStream_t st, const ParticleEventArgs& a) {
     hipLaunchKernelGGL(k_particle_events_finish, dim3(1), dim3(64), 0, st, a);
 }
 
-// the policy against the dynamics slot (and, RbfController, the policy slot)
-int check_policy(pilco_ctx* ctx, const pilco_policy* policy) {
-    const Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
-    if (!policy) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: null policy");
-    const int E = s.E, D = s.D, U = D - E;
-    if (policy->state_dim != E || policy->control_dim != U || U < 0 || D > MAX_D)
-        return fail(ctx, PILCO_E_SHAPE, "rollout_particles: policy dims do not match the model (state_dim must be E, control_dim D-E)");
-    if (policy->kind < 0 || policy->kind > 2) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: unknown policy kind");
-    if (policy->kind == PILCO_POLICY_NONE && U != 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: policy NONE needs D == E");
-    if (policy->kind != PILCO_POLICY_NONE && U == 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: a policy needs control_dim > 0");
-    if (policy->kind == PILCO_POLICY_LINEAR && (!policy->W || !policy->b))
-        return fail(ctx, PILCO_E_SHAPE, "rollout_particles: linear policy needs W and b");
-    if (policy->kind == PILCO_POLICY_RBF) {
-        const Slot& ps = ctx->slot[PILCO_SLOT_POLICY];
-        if (!ps.factor_valid || ps.M > 0) return fail(ctx, PILCO_E_STATE, "rollout_particles: RBF policy slot has no current (exact) factorisation");
-        if (ps.D != E || ps.E != U) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: RBF policy GP must map state_dim -> control_dim");
-    }
-    return PILCO_OK;
-}
-
-// the policy's parameters into the staging vector hp (W[U*E] b[U] maxact[U]) and the action kernel's arguments; dev: where hp goes
-void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double>& hp, size_t& off, const double* dev,
-                  ParticleHeadArgs& ha) {
-    const Slot &s = ctx->slot[PILCO_SLOT_DYNAMICS], &ps = ctx->slot[PILCO_SLOT_POLICY];
-    const int E = s.E, U = s.D - s.E;
-    ha.E = E; ha.U = U; ha.kind = policy->kind; ha.squash = policy->squash;
-    if (policy->kind == PILCO_POLICY_LINEAR) {
-        memcpy(&hp[off], policy->W, sizeof(double) * U * E);
-        ha.W = dev + off; off += (size_t)U * E;
-        memcpy(&hp[off], policy->b, sizeof(double) * U);
-        ha.b = dev + off; off += U;
-    }
-    for (int u = 0; u < U; ++u) hp[off + u] = policy->max_action ? policy->max_action[u] : 1.0;
-    ha.maxact = dev + off; off += U;
-    if (policy->kind == PILCO_POLICY_RBF) {
-        ha.pc = ps.Xt.p; ha.pls = ps.ls.p; ha.pvar = ps.var.p; ha.pbeta = ps.beta.p;
-        ha.pn = ps.N; ha.pnpad = ps.Npad;
-    }
-}
-
-// what pilco_rollout_particles refuses about the slot, the context, P and H
-int check_particle_state(pilco_ctx* ctx, int P, int H) {
-    if (int r = check_slot(ctx, PILCO_SLOT_DYNAMICS)) return r;
-    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
-    if (ctx->nranks != 1 || ctx->comm || s.shW > 1) return fail(ctx, PILCO_E_STATE, "rollout_particles: single rank only");
-    if (!s.has_data || !s.has_hyp) return fail(ctx, PILCO_E_STATE, "rollout_particles needs set_data and set_hyp first");
-    if (s.user_factors)
-        return fail(ctx, PILCO_E_STATE, "rollout_particles: the slot holds factors set by pilco_gp_set_factors, not its own factorisation");
-    if (P <= 0 || H < 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: P must be positive and H non-negative");
-    return PILCO_OK;
-}
-
-// ... and about the policy and the reward terms
-int check_particle_terms(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards) {
-    if (int r = check_policy(ctx, policy)) return r;
-    if (n_rewards < 0 || n_rewards > MAX_REWARD_TERMS || (n_rewards > 0 && !rewards))
-        return fail(ctx, PILCO_E_SHAPE, "rollout_particles: 0..4 reward terms supported");
-    for (int i = 0; i < n_rewards; ++i) {
-        if (rewards[i].kind != PILCO_REWARD_EXPONENTIAL && rewards[i].kind != PILCO_REWARD_LINEAR)
-            return fail(ctx, PILCO_E_SHAPE, "reward: unknown kind");
-        if (!rewards[i].W) return fail(ctx, PILCO_E_SHAPE, "reward: W is required");
-    }
-    return PILCO_OK;
-}
-
-// the reward terms into the staging vector hp and the draw kernel's arguments; dev: where hp goes
-void stage_rewards(const pilco_reward_term* rewards, int n_rewards, int E, std::vector<double>& hp, size_t& off, const double* dev,
-                   ParticleReward* rw) {
-    for (int i = 0; i < n_rewards; ++i) {
-        ParticleReward& r = rw[i];
-        r.kind = rewards[i].kind;
-        r.coef = rewards[i].coef;
-        if (r.kind == PILCO_REWARD_EXPONENTIAL) {
-            memcpy(&hp[off], rewards[i].W, sizeof(double) * E * E);
-            r.W = dev + off; off += (size_t)E * E;
-            if (rewards[i].t) memcpy(&hp[off], rewards[i].t, sizeof(double) * E);   // (NULL: the zeros hp holds)
-            r.t = dev + off; off += E;
-        } else {
-            memcpy(&hp[off], rewards[i].W, sizeof(double) * E);
-            r.W = dev + off; off += E;
-            r.t = r.W;
-        }
-    }
-}
-
-// pilco_rollout_particles and pilco_rollout_particles_events: with n_events == 0 exactly the launches of the former
-static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
-                             const double* x0, int P, int H, const double* eps, unsigned long long seed, int observation_noise,
-                             double* mean, double* cov, double* reward_steps, double* particles, double* eps_out,
-                             const pilco_event* events, int n_events, long long* counts, int* first_hit) {
-    if (int r = check_particle_state(ctx, P, H)) return r;
-    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
-    if (!x0 || !mean || !cov) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: null x0, mean or cov");
-    if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
-    const int E = s.E, D = s.D, U = D - E;
-    if (const char* why = event_table_refusal(events, n_events, counts, E))
-        return fail(ctx, PILCO_E_SHAPE, std::string("rollout_particles: ") + why);
-    HIPCHK(hipSetDevice(ctx->device));
-    if (!s.factor_valid)
-        if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
-    if (!s.pred) s.pred = new PredictWork();
-    PredictWork& pw = *s.pred;
-    hipStream_t st = ctx->st;
-    const PredictModel md = predict_model_of(s, 0, E);
+// pilco_rollout_particles and pilco_rollout_particles_events: with n_events == 0 exactly the launches of the former.  The frame
+// (particle_frame.hip) holds what surrounds the step loop
+static int rollout_particles(pilco_ctx* ctx, const ParticleCall& c) {
+    ParticleFrame f{ctx, c};
+    if (int r = f.check("rollout_particles")) return r;
+    const int E = f.E, D = f.D, P = c.P, H = c.H;
+    const size_t PE = f.PE;
+    ParticleTailArgs ta{};
+    if (int r = f.open(c.particles ? H + 1 : 2, (H > 0 && (c.eps || c.eps_out)) ? (size_t)H * PE : 0, ta.rw)) return r;
+    PredictWork& pw = *f.work;
+    hipStream_t st = f.st;
+    const PredictModel md = predict_model_of(ctx->slot[PILCO_SLOT_DYNAMICS], 0, E);
     const int npad = md.npad;
     const int ntc_max = std::min(round_up(P, 64), predict_chunk_cap(E, npad));
-    const size_t PE = (size_t)P * E;
-    const int Q = E + E * E + 1, nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
-    const int nslab = particles ? H + 1 : 2;
-    const bool keep_eps = H > 0 && (eps || eps_out);
-    // parameters: W[U*E] b[U] maxact[U], then per reward W[E*E] t[E] (exponential) or W[E] (linear)
-    std::vector<double> hp(particle_par_doubles(E, U), 0.0);
-    std::vector<double> hstats((size_t)(H + 1) * Q);
     ENSURE(pw.Xt, (size_t)D * ntc_max);
     ENSURE(pw.Ks, (size_t)E * ntc_max * npad);
     ENSURE(pw.out, (size_t)2 * E * ntc_max);
-    ENSURE(pw.pt_x, (size_t)nslab * PE);
-    if (keep_eps) ENSURE(pw.pt_eps, (size_t)H * PE);
     ENSURE(pw.pt_rew, (size_t)P);
-    ENSURE(pw.pt_part, (size_t)nblk * Q);
-    ENSURE(pw.pt_stats, hstats.size());
-    ENSURE(pw.pt_par, hp.size());
-    // the events' integers live in buffers of doubles: first hits [P][K] int, the blocks' counts [nblk][K] int, counts [H+1][K] long long
-    const int K = n_events;
-    const size_t fh_bytes = sizeof(int) * (size_t)P * K;
-    if (K > 0) {
-        if (first_hit) ENSURE(pw.pt_ev_first, (fh_bytes + 7) / 8);
-        ENSURE(pw.pt_ev_part, (sizeof(int) * (size_t)nblk * K + 7) / 8);
-        ENSURE(pw.pt_ev_counts, (size_t)(H + 1) * K);
-    }
+    if (int r = f.upload()) return r;
 
-    ParticleHeadArgs ha{};
-    ParticleTailArgs ta{};
-    size_t off = 0;
-    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ha);
-    ta.n_rewards = n_rewards;
-    stage_rewards(rewards, n_rewards, E, hp, off, pw.pt_par.p, ta.rw);
-    StreamDrain drain{st};
-    // one upload: parameters, initial particles, the caller's draws
-    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
-    if (eps && H > 0) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
-
-    ta.E = E; ta.seed = seed;
-    ta.noise = observation_noise ? s.noise.p : nullptr;
+    ParticleHeadArgs& ha = f.ha;
+    ta.n_rewards = c.n_rewards; ta.E = E; ta.seed = c.seed;
+    ta.noise = c.observation_noise ? ctx->slot[PILCO_SLOT_DYNAMICS].noise.p : nullptr;
     ta.rew = pw.pt_rew.p;
-    ParticleStatArgs sa{};
-    sa.P = P; sa.E = E; sa.nblk = nblk; sa.part = pw.pt_part.p;
-    auto slab = [&](int t) { return pw.pt_x.p + (size_t)(particles ? t : (t & 1)) * PE; };
-    auto stats = [&](int t, bool with_reward) {   // moments of the states after t steps (and the mean reward of step t - 1)
-        sa.x = slab(t);
-        sa.rew = with_reward ? pw.pt_rew.p : nullptr;
-        sa.out = pw.pt_stats.p + (size_t)t * Q;
-        launch_particle_stats(st, sa);
-    };
-    ParticleEventArgs ea{};
-    if (K > 0) {
-        ea.P = P; ea.E = E; ea.K = K; ea.nblk = nblk;
-        ea.first_hit = first_hit ? reinterpret_cast<int*>(pw.pt_ev_first.p) : nullptr;
-        ea.part = reinterpret_cast<int*>(pw.pt_ev_part.p);
-        for (int k = 0; k < K; ++k) ea.ev[k] = events[k];
-        if (first_hit) HIPCHK(hipMemsetAsync(pw.pt_ev_first.p, 0xFF, fh_bytes, st));   // every entry -1
-    }
-    auto count_events = [&](int t) {   // the hits of the states after t steps
-        if (K == 0) return;
-        ea.x = slab(t);
-        ea.t = t;
-        ea.counts = reinterpret_cast<long long*>(pw.pt_ev_counts.p) + (size_t)t * K;
-        launch_particle_events(st, ea);
-    };
-    stats(0, false);
-    count_events(0);
+    if (int r = f.state(0, nullptr)) return r;
     for (int t = 0; t < H; ++t) {
-        ha.x = ta.x = slab(t);
-        ta.xn = slab(t + 1);
+        ha.x = ta.x = f.slab(t);
+        ta.xn = f.slab(t + 1);
         ta.t = t;
-        ta.eps_in = eps ? pw.pt_eps.p + (size_t)t * PE : nullptr;
-        ta.eps_out = (!eps && eps_out) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
+        ta.eps_in = c.eps ? pw.pt_eps.p + (size_t)t * PE : nullptr;
+        ta.eps_out = (!c.eps && c.eps_out) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
         for (int p0 = 0; p0 < P; p0 += ntc_max) {
             const int ntc = std::min(ntc_max, P - p0), ldt = round_up(ntc, 64);
             double *out_mean = pw.out.p, *out_var = pw.out.p + (size_t)E * ldt;
@@ -372,26 +225,14 @@ static int rollout_particles(pilco_ctx* ctx, const pilco_policy* policy, const p
             ta.mu = out_mean; ta.var = out_var; ta.p0 = p0; ta.ntc = ntc; ta.ldt = ldt;
             launch_particle_tail(st, ta);
         }
-        stats(t + 1, true);   // (its reward word: the mean reward of the pre-step states of step t)
-        count_events(t + 1);
+        if (int r = f.state(t + 1, pw.pt_rew.p)) return r;
     }
-    HIPCHK(hipGetLastError());
     // one download, one synchronisation
-    HIPCHK(hipMemcpyAsync(hstats.data(), pw.pt_stats.p, sizeof(double) * hstats.size(), hipMemcpyDeviceToHost, st));
-    if (particles) HIPCHK(hipMemcpyAsync(particles, pw.pt_x.p, sizeof(double) * (H + 1) * PE, hipMemcpyDeviceToHost, st));
-    if (eps_out && !eps && H > 0) HIPCHK(hipMemcpyAsync(eps_out, pw.pt_eps.p, sizeof(double) * H * PE, hipMemcpyDeviceToHost, st));
-    if (K > 0) {
-        HIPCHK(hipMemcpyAsync(counts, pw.pt_ev_counts.p, sizeof(long long) * (H + 1) * K, hipMemcpyDeviceToHost, st));
-        if (first_hit) HIPCHK(hipMemcpyAsync(first_hit, pw.pt_ev_first.p, fh_bytes, hipMemcpyDeviceToHost, st));
-    }
+    if (int r = f.download(c.particles, c.eps ? nullptr : c.eps_out)) return r;
+    if (int r = f.download_events(c.counts, c.first_hit)) return r;
     HIPCHK(hipStreamSynchronize(st));
-    if (eps_out && eps && H > 0) memcpy(eps_out, eps, sizeof(double) * H * PE);
-    for (int t = 0; t <= H; ++t) {
-        const double* row = &hstats[(size_t)t * Q];
-        memcpy(mean + (size_t)t * E, row, sizeof(double) * E);
-        memcpy(cov + (size_t)t * E * E, row + E, sizeof(double) * E * E);
-        if (t > 0 && reward_steps) reward_steps[t - 1] = row[Q - 1];
-    }
+    if (c.eps_out && c.eps && H > 0) memcpy(c.eps_out, c.eps, sizeof(double) * H * PE);
+    f.finish();
     return PILCO_OK;
 }
 
@@ -399,8 +240,8 @@ extern "C" int pilco_rollout_particles(pilco_ctx* ctx, const pilco_policy* polic
                                        const double* x0, int P, int H, const double* eps, unsigned long long seed,
                                        int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
                                        double* eps_out) {
-    return rollout_particles(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps,
-                             particles, eps_out, nullptr, 0, nullptr, nullptr);
+    return rollout_particles(ctx, {policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps, particles,
+                                   eps_out, nullptr, 0, nullptr, nullptr});
 }
 
 extern "C" int pilco_rollout_particles_events(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards,
@@ -408,8 +249,8 @@ extern "C" int pilco_rollout_particles_events(pilco_ctx* ctx, const pilco_policy
                                               unsigned long long seed, int observation_noise, double* mean, double* cov,
                                               double* reward_steps, double* particles, double* eps_out, const pilco_event* events,
                                               int n_events, long long* counts, int* first_hit) {
-    return rollout_particles(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps,
-                             particles, eps_out, events, n_events, counts, first_hit);
+    return rollout_particles(ctx, {policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps, particles,
+                                   eps_out, events, n_events, counts, first_hit});
 }
 
 extern "C" int pilco_debug_particle_actions(pilco_ctx* ctx, const pilco_policy* policy, const double* x, int P, double* u) {
@@ -435,7 +276,7 @@ extern "C" int pilco_debug_particle_actions(pilco_ctx* ctx, const pilco_policy* 
     StreamDrain drain{ctx->st};
     HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, ctx->st));
     HIPCHK(hipMemcpyAsync(pw.pt_x.p, x, sizeof(double) * P * E, hipMemcpyHostToDevice, ctx->st));
-    hipLaunchKernelGGL(k_particle_head, dim3((ldt + 255) / 256), dim3(256), 0, ctx->st, ha);
+    launch_particle_head(ctx->st, ha);
     HIPCHK(hipGetLastError());
     std::vector<double> ut((size_t)U * ldt);
     HIPCHK(hipMemcpyAsync(ut.data(), pw.Xt.p + (size_t)E * ldt, sizeof(double) * ut.size(), hipMemcpyDeviceToHost, ctx->st));

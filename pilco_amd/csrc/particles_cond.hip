@@ -12,7 +12,7 @@
 //   predict_points_w_device  W = Op K*, written into slab t of the row history Wh [H][nops][E][ldt][npad]
 //   k_particle_cond_step     the t + 1 signed dot products, the kernel values, the factor row, the draw, the update, the reward
 // A group runs all H steps, then the next group; the statistics and events of every state run after the last group over all
-// particles, in the order of pilco_rollout_particles: grouping changes no bit.
+// particles, by the frame every forward rollout stands on (ParticleFrame::state, particle_frame.hip): grouping changes no bit.
 //
 // ORDER OF THE SUMS (a function of (npad, nops, t) only; no atomics of any kind).
 //   dot product of two rows: lane l of the wave owns the element pairs (2 q, 2 q + 1), q = l + 64 m, m = 0, 1, ..; it adds
@@ -230,13 +230,16 @@ extern "C" int pilco_rollout_particles_cond(pilco_ctx* ctx, const pilco_policy* 
                                             int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
                                             double* eps_out, const pilco_event* events, int n_events, long long* counts,
                                             int* first_hit, double jitter, const double* eps_obs, const pilco_cond_out* out) {
-    if (int r = check_particle_state(ctx, P, H)) return r;
+    // everything the caller gets back is staged here: nothing is written unless every pivot was positive.  (Before the frame,
+    // which drains the stream when it leaves)
+    std::vector<double> h_parts, h_eps, h_zeta, h_lam, h_cov;
+    std::vector<int> h_info, h_first;
+    std::vector<long long> h_counts;
+    ParticleFrame f{ctx, {policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps, particles, eps_out,
+                          events, n_events, counts, first_hit}};
+    if (int r = f.check("rollout_particles_cond")) return r;
     Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
-    if (!x0 || !mean || !cov) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_cond: null x0, mean or cov");
-    if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
-    const int E = s.E, D = s.D, U = D - E;
-    if (const char* why = event_table_refusal(events, n_events, counts, E))
-        return fail(ctx, PILCO_E_SHAPE, std::string("rollout_particles_cond: ") + why);
+    const int E = f.E, D = f.D, K = f.K;
     if (H > PILCO_MAX_COND_STEPS) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_cond: H must be at most 128 (PILCO_MAX_COND_STEPS)");
     if (!(jitter >= 0.0) || !std::isfinite(jitter)) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_cond: jitter must be finite and >= 0");
     const bool noisy = observation_noise != 0, sparse = s.M > 0;
@@ -252,27 +255,17 @@ extern "C" int pilco_rollout_particles_cond(pilco_ctx* ctx, const pilco_policy* 
         return fail(ctx, PILCO_E_SHAPE, "rollout_particles_cond: a group of 64 particles needs " + std::to_string(pl.footprint) +
                                             " doubles, over the budget of " + std::to_string(budget) +
                                             " (PILCO_PARTICLE_COND_BUDGET); the largest H that fits is " + std::to_string(pl.H_fit));
-    HIPCHK(hipSetDevice(ctx->device));
-    if (!s.factor_valid)
-        if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
-    if (!s.pred) s.pred = new PredictWork();
-    PredictWork& pw = *s.pred;
-    hipStream_t st = ctx->st;
+    const size_t PE = f.PE, tri = cond_tri(H);
+    ParticleCondArgs ca{};
+    if (int r = f.open(H + 1, std::max((size_t)H * PE, (size_t)1), ca.rw)) return r;
+    PredictWork& pw = *f.work;
+    hipStream_t st = f.st;
     const PredictModel md = predict_model_of(s, 0, E);
     const int npad = md.npad;
     if (npad != npad_m || predict_jac_nops(md) != nops) return fail(ctx, PILCO_E_STATE, "rollout_particles_cond: the model's padding changed under the plan");
-    const int G = pl.G, K = n_events;
-    const size_t PE = (size_t)P * E, tri = cond_tri(H);
-    const int Q = E + E * E + 1, nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
-    std::vector<double> hp(particle_par_doubles(E, U), 0.0);
-    std::vector<double> hstats((size_t)(H + 1) * Q);
-    ENSURE(pw.pt_x, (size_t)(H + 1) * PE);
-    ENSURE(pw.pt_eps, std::max((size_t)H * PE, (size_t)1));
+    const int G = pl.G;
     if (noisy) ENSURE(pw.pc2_zeta, std::max((size_t)H * PE, (size_t)1));
     ENSURE(pw.pc2_rew, std::max((size_t)H * P, (size_t)1));
-    ENSURE(pw.pt_part, (size_t)nblk * Q);
-    ENSURE(pw.pt_stats, hstats.size());
-    ENSURE(pw.pt_par, hp.size());
     if (H > 0) {
         ENSURE(pw.Ks, (size_t)E * G * npad);
         ENSURE(pw.out, (size_t)2 * E * G);
@@ -282,33 +275,16 @@ extern "C" int pilco_rollout_particles_cond(pilco_ctx* ctx, const pilco_policy* 
         if (o_cov) ENSURE(pw.pc2_cov, (size_t)G * E * tri);
         ENSURE(pw.pc2_info, (sizeof(int) * (size_t)G * E + 7) / 8);
     }
-    const size_t fh_bytes = sizeof(int) * (size_t)P * K;
-    if (K > 0) {
-        if (first_hit) ENSURE(pw.pt_ev_first, (fh_bytes + 7) / 8);
-        ENSURE(pw.pt_ev_part, (sizeof(int) * (size_t)nblk * K + 7) / 8);
-        ENSURE(pw.pt_ev_counts, (size_t)(H + 1) * K);
-    }
-
-    ParticleHeadArgs ha{};
-    ParticleCondArgs ca{};
-    size_t off = 0;
-    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ha);
-    ca.n_rewards = n_rewards;
-    stage_rewards(rewards, n_rewards, E, hp, off, pw.pt_par.p, ca.rw);
-    // everything the caller gets back is staged here: nothing is written unless every pivot was positive
-    std::vector<double> h_parts(particles ? (size_t)(H + 1) * PE : 0), h_eps((eps_out && !eps) ? (size_t)H * PE : 0);
-    std::vector<double> h_zeta((o_zeta && !eps_obs) ? (size_t)H * PE : 0);
-    std::vector<double> h_lam(o_fac ? PE * tri : 0), h_cov(o_cov ? PE * tri : 0);
-    std::vector<int> h_info(H > 0 ? PE : 0), h_first(first_hit ? (size_t)P * K : 0);
-    std::vector<long long> h_counts((size_t)(H + 1) * K);
-    StreamDrain drain{st};
-    // one upload: parameters, initial particles, the caller's draws
-    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
-    if (eps && H > 0) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
+    h_parts.resize(particles ? (size_t)(H + 1) * PE : 0); h_eps.resize((eps_out && !eps) ? (size_t)H * PE : 0);
+    h_zeta.resize((o_zeta && !eps_obs) ? (size_t)H * PE : 0);
+    h_lam.resize(o_fac ? PE * tri : 0); h_cov.resize(o_cov ? PE * tri : 0);
+    h_info.resize(H > 0 ? PE : 0); h_first.resize(first_hit ? (size_t)P * K : 0);
+    h_counts.resize((size_t)(H + 1) * K);
+    if (int r = f.upload()) return r;
     if (noisy && eps_obs && H > 0) HIPCHK(hipMemcpyAsync(pw.pc2_zeta.p, eps_obs, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
 
-    auto slab = [&](int t) { return pw.pt_x.p + (size_t)t * PE; };
+    ParticleHeadArgs& ha = f.ha;
+    ca.n_rewards = n_rewards;
     ca.H = H; ca.P = P; ca.E = E; ca.D = D; ca.npad = npad; ca.nops = nops; ca.seed = seed; ca.jitter = jitter;
     ca.ls = md.ls; ca.sf2 = md.sf2; ca.noise = md.sn2;
     ca.eps = pw.pt_eps.p; ca.eps_given = eps ? 1 : 0;
@@ -325,8 +301,8 @@ extern "C" int pilco_rollout_particles_cond(pilco_ctx* ctx, const pilco_policy* 
         ha.p0 = ca.p0 = g0; ha.ntc = ca.ntc = ntc; ha.ldt = ca.ldt = ldt;
         ca.Wh = pw.pc2_Wh.p; ca.Xh = pw.pc2_Xh.p; ca.mu = out_mean;
         for (int t = 0; t < H; ++t) {
-            ha.x = ca.x = slab(t);
-            ca.xn = slab(t + 1);
+            ha.x = ca.x = f.slab(t);
+            ca.xn = f.slab(t + 1);
             ca.t = t;
             ca.rew = pw.pc2_rew.p + (size_t)t * P;
             ha.Xt = pw.pc2_Xh.p + (size_t)t * sX;
@@ -345,38 +321,12 @@ extern "C" int pilco_rollout_particles_cond(pilco_ctx* ctx, const pilco_policy* 
     }
 
     // the statistics and events of every state, over all particles: the launches and the order of pilco_rollout_particles
-    ParticleStatArgs sa{};
-    sa.P = P; sa.E = E; sa.nblk = nblk; sa.part = pw.pt_part.p;
-    ParticleEventArgs ea{};
-    if (K > 0) {
-        ea.P = P; ea.E = E; ea.K = K; ea.nblk = nblk;
-        ea.first_hit = first_hit ? reinterpret_cast<int*>(pw.pt_ev_first.p) : nullptr;
-        ea.part = reinterpret_cast<int*>(pw.pt_ev_part.p);
-        for (int k = 0; k < K; ++k) ea.ev[k] = events[k];
-        if (first_hit) HIPCHK(hipMemsetAsync(pw.pt_ev_first.p, 0xFF, fh_bytes, st));   // every entry -1
-    }
-    for (int t = 0; t <= H; ++t) {
-        sa.x = slab(t);
-        sa.rew = t > 0 ? pw.pc2_rew.p + (size_t)(t - 1) * P : nullptr;
-        sa.out = pw.pt_stats.p + (size_t)t * Q;
-        launch_particle_stats(st, sa);
-        if (K > 0) {
-            ea.x = slab(t);
-            ea.t = t;
-            ea.counts = reinterpret_cast<long long*>(pw.pt_ev_counts.p) + (size_t)t * K;
-            launch_particle_events(st, ea);
-        }
-    }
-    HIPCHK(hipGetLastError());
+    for (int t = 0; t <= H; ++t)
+        if (int r = f.state(t, t > 0 ? pw.pc2_rew.p + (size_t)(t - 1) * P : nullptr)) return r;
     // one download into staging memory, one synchronisation
-    HIPCHK(hipMemcpyAsync(hstats.data(), pw.pt_stats.p, sizeof(double) * hstats.size(), hipMemcpyDeviceToHost, st));
-    if (particles) HIPCHK(hipMemcpyAsync(h_parts.data(), pw.pt_x.p, sizeof(double) * (H + 1) * PE, hipMemcpyDeviceToHost, st));
-    if (!h_eps.empty()) HIPCHK(hipMemcpyAsync(h_eps.data(), pw.pt_eps.p, sizeof(double) * H * PE, hipMemcpyDeviceToHost, st));
+    if (int r = f.download(particles ? h_parts.data() : nullptr, h_eps.empty() ? nullptr : h_eps.data())) return r;
     if (!h_zeta.empty()) HIPCHK(hipMemcpyAsync(h_zeta.data(), pw.pc2_zeta.p, sizeof(double) * H * PE, hipMemcpyDeviceToHost, st));
-    if (K > 0) {
-        HIPCHK(hipMemcpyAsync(h_counts.data(), pw.pt_ev_counts.p, sizeof(long long) * (H + 1) * K, hipMemcpyDeviceToHost, st));
-        if (first_hit) HIPCHK(hipMemcpyAsync(h_first.data(), pw.pt_ev_first.p, fh_bytes, hipMemcpyDeviceToHost, st));
-    }
+    if (int r = f.download_events(h_counts.data(), h_first.data())) return r;
     HIPCHK(hipStreamSynchronize(st));
     // the earliest step with a pivot that was not positive; at that step the lowest particle, then the lowest output
     long bad = -1;
@@ -393,17 +343,12 @@ extern "C" int pilco_rollout_particles_cond(pilco_ctx* ctx, const pilco_policy* 
     if (o_zeta && H > 0) memcpy(o_zeta, eps_obs ? eps_obs : h_zeta.data(), sizeof(double) * H * PE);
     if (K > 0) {
         memcpy(counts, h_counts.data(), sizeof(long long) * h_counts.size());
-        if (first_hit) memcpy(first_hit, h_first.data(), fh_bytes);
+        if (first_hit) memcpy(first_hit, h_first.data(), f.fh_bytes);
     }
     for (size_t k = 0; k < PE && H > 0; ++k) {
         if (o_fac) cond_unpack(h_lam.data() + k * tri, H, o_fac + k * (size_t)H * H);
         if (o_cov) cond_unpack(h_cov.data() + k * tri, H, o_cov + k * (size_t)H * H);
     }
-    for (int t = 0; t <= H; ++t) {
-        const double* row = &hstats[(size_t)t * Q];
-        memcpy(mean + (size_t)t * E, row, sizeof(double) * E);
-        memcpy(cov + (size_t)t * E * E, row + E, sizeof(double) * E * E);
-        if (t > 0 && reward_steps) reward_steps[t - 1] = row[Q - 1];
-    }
+    f.finish();
     return PILCO_OK;
 }

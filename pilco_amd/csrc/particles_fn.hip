@@ -15,7 +15,7 @@
 // STEP, once per step:
 //   k_particle_head (particles.hip)  the actions and the transposed block [x, u] of ALL particles (ldt = Ppad)
 //   k_particle_fn_step               f, the update, the optional noise draw, the reward of the pre-step state
-//   the statistics and event launches of pilco_rollout_particles (launch_particle_stats, launch_particle_events)
+//   the statistics and event launches of every forward rollout (ParticleFrame::state, particle_frame.hip)
 // k_particle_fn_step: a workgroup of FN_WAVES = 8 waves owns 64 particles (one per lane) and ONE output e.  The training points, then
 // the features, are walked in tiles of FN_TILE = 64 staged through LDS (points [i][D], frequencies [l][D], phases [l]: every
 // lane of a wave reads the same word, a broadcast); V and Wt are read straight from memory, 64 consecutive particles of one
@@ -260,119 +260,52 @@ extern "C" int pilco_rollout_particles_fn(pilco_ctx* ctx, const pilco_policy* po
                                           int observation_noise, double* mean, double* cov, double* reward_steps, double* particles,
                                           double* eps_out, const pilco_event* events, int n_events, long long* counts,
                                           int* first_hit, const pilco_function_draws* draws, const pilco_function_draws_out* draws_out) {
-    if (int r = check_particle_state(ctx, P, H)) return r;
-    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
-    if (!x0 || !mean || !cov) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_fn: null x0, mean or cov");
-    if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
-    const int E = s.E, D = s.D, U = D - E;
-    if (const char* why = event_table_refusal(events, n_events, counts, E))
-        return fail(ctx, PILCO_E_SHAPE, std::string("rollout_particles_fn: ") + why);
+    const bool noisy = observation_noise != 0;
+    FnDrawsStage stage;   // (before the frame, which drains the stream when it leaves)
+    ParticleFrame f{ctx, {policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, mean, cov, reward_steps, particles, eps_out,
+                          events, n_events, counts, first_hit}};
+    if (int r = f.check("rollout_particles_fn")) return r;
     FnPlan pl{};
     if (int r = fn_plan(ctx, "rollout_particles_fn", draws, P, pl)) return r;
-    const int N = pl.N, npad = pl.npad, L = pl.L, Lpad = pl.Lpad, Ppad = pl.Ppad;
-    HIPCHK(hipSetDevice(ctx->device));
-    if (!s.factor_valid)
-        if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
-    if (!s.pred) s.pred = new PredictWork();
-    PredictWork& pw = *s.pred;
-    hipStream_t st = ctx->st;
-    const bool noisy = observation_noise != 0;
-    const size_t PE = (size_t)P * E;
-    const int Q = E + E * E + 1, nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
-    const int nslab = particles ? H + 1 : 2;
+    const int E = f.E, D = f.D, Ppad = pl.Ppad;
+    const size_t PE = f.PE;
     const bool keep_eps = noisy && H > 0 && (eps || eps_out);
-    std::vector<double> hp(particle_par_doubles(E, U), 0.0);
-    std::vector<double> hstats((size_t)(H + 1) * Q);
-    ENSURE(pw.Xt, (size_t)D * Ppad);
-    ENSURE(pw.pt_x, (size_t)nslab * PE);
-    if (keep_eps) ENSURE(pw.pt_eps, (size_t)H * PE);
-    ENSURE(pw.pt_rew, (size_t)P);
-    ENSURE(pw.pt_part, (size_t)nblk * Q);
-    ENSURE(pw.pt_stats, hstats.size());
-    ENSURE(pw.pt_par, hp.size());
-    const int K = n_events;
-    const size_t fh_bytes = sizeof(int) * (size_t)P * K;
-    if (K > 0) {
-        if (first_hit) ENSURE(pw.pt_ev_first, (fh_bytes + 7) / 8);
-        ENSURE(pw.pt_ev_part, (sizeof(int) * (size_t)nblk * K + 7) / 8);
-        ENSURE(pw.pt_ev_counts, (size_t)(H + 1) * K);
-    }
-
-    ParticleHeadArgs ha{};
     ParticleFnArgs fa{};
-    size_t off = 0;
-    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ha);
-    fa.n_rewards = n_rewards;
-    stage_rewards(rewards, n_rewards, E, hp, off, pw.pt_par.p, fa.rw);
-    StreamDrain drain{st};
-    // one upload: parameters, initial particles, the caller's draws
-    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
-    if (keep_eps && eps) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
+    if (int r = f.open(particles ? H + 1 : 2, keep_eps ? (size_t)H * PE : 0, fa.rw)) return r;
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
+    PredictWork& pw = *f.work;
+    hipStream_t st = f.st;
+    ENSURE(pw.Xt, (size_t)D * Ppad);
+    ENSURE(pw.pt_rew, (size_t)P);
+    if (int r = f.upload()) return r;
     if (int r = fn_setup(ctx, pl, draws, draws_out, seed)) return r;
 
-    fa.E = E; fa.D = D; fa.N = N; fa.npad = npad; fa.L = L; fa.Lpad = Lpad; fa.P = P; fa.Ppad = Ppad; fa.seed = seed;
+    ParticleHeadArgs& ha = f.ha;
+    fa.n_rewards = n_rewards;
+    fa.E = E; fa.D = D; fa.N = pl.N; fa.npad = pl.npad; fa.L = pl.L; fa.Lpad = pl.Lpad; fa.P = P; fa.Ppad = Ppad; fa.seed = seed;
     fa.Xq = pw.Xt.p; fa.ldq = Ppad; fa.Xt = s.Xt.p; fa.ls = s.ls.p; fa.sf2 = s.var.p;
     fa.noise = noisy ? s.noise.p : nullptr;
     fa.om = pw.fn_om.p; fa.ph = pw.fn_ph.p; fa.Wt = pw.fn_Wt.p; fa.V = pw.fn_V.p;
     fa.rew = pw.pt_rew.p;
-    ParticleStatArgs sa{};
-    sa.P = P; sa.E = E; sa.nblk = nblk; sa.part = pw.pt_part.p;
-    auto slab = [&](int t) { return pw.pt_x.p + (size_t)(particles ? t : (t & 1)) * PE; };
-    auto stats = [&](int t, bool with_reward) {
-        sa.x = slab(t);
-        sa.rew = with_reward ? pw.pt_rew.p : nullptr;
-        sa.out = pw.pt_stats.p + (size_t)t * Q;
-        launch_particle_stats(st, sa);
-    };
-    ParticleEventArgs ea{};
-    if (K > 0) {
-        ea.P = P; ea.E = E; ea.K = K; ea.nblk = nblk;
-        ea.first_hit = first_hit ? reinterpret_cast<int*>(pw.pt_ev_first.p) : nullptr;
-        ea.part = reinterpret_cast<int*>(pw.pt_ev_part.p);
-        for (int k = 0; k < K; ++k) ea.ev[k] = events[k];
-        if (first_hit) HIPCHK(hipMemsetAsync(pw.pt_ev_first.p, 0xFF, fh_bytes, st));   // every entry -1
-    }
-    auto count_events = [&](int t) {
-        if (K == 0) return;
-        ea.x = slab(t);
-        ea.t = t;
-        ea.counts = reinterpret_cast<long long*>(pw.pt_ev_counts.p) + (size_t)t * K;
-        launch_particle_events(st, ea);
-    };
-    stats(0, false);
-    count_events(0);
+    if (int r = f.state(0, nullptr)) return r;
     ha.Xt = pw.Xt.p; ha.p0 = 0; ha.ntc = P; ha.ldt = Ppad;
     for (int t = 0; t < H; ++t) {
-        ha.x = fa.x = slab(t);
-        fa.xn = slab(t + 1);
+        ha.x = fa.x = f.slab(t);
+        fa.xn = f.slab(t + 1);
         fa.t = t;
         fa.eps_in = (noisy && eps) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
         fa.eps_out = (noisy && !eps && eps_out) ? pw.pt_eps.p + (size_t)t * PE : nullptr;
         launch_particle_head(st, ha);
         launch_fn_step(st, fa, P);
-        stats(t + 1, true);
-        count_events(t + 1);
+        if (int r = f.state(t + 1, pw.pt_rew.p)) return r;
     }
-    HIPCHK(hipGetLastError());
     // one download, one synchronisation
-    HIPCHK(hipMemcpyAsync(hstats.data(), pw.pt_stats.p, sizeof(double) * hstats.size(), hipMemcpyDeviceToHost, st));
-    if (particles) HIPCHK(hipMemcpyAsync(particles, pw.pt_x.p, sizeof(double) * (H + 1) * PE, hipMemcpyDeviceToHost, st));
-    if (noisy && eps_out && !eps && H > 0) HIPCHK(hipMemcpyAsync(eps_out, pw.pt_eps.p, sizeof(double) * H * PE, hipMemcpyDeviceToHost, st));
-    if (K > 0) {
-        HIPCHK(hipMemcpyAsync(counts, pw.pt_ev_counts.p, sizeof(long long) * (H + 1) * K, hipMemcpyDeviceToHost, st));
-        if (first_hit) HIPCHK(hipMemcpyAsync(first_hit, pw.pt_ev_first.p, fh_bytes, hipMemcpyDeviceToHost, st));
-    }
-    FnDrawsStage stage;
+    if (int r = f.download(particles, (noisy && !eps) ? eps_out : nullptr)) return r;
+    if (int r = f.download_events(counts, first_hit)) return r;
     if (int r = fn_draws_download(ctx, pl, draws_out, stage)) return r;
     HIPCHK(hipStreamSynchronize(st));
     if (noisy && eps_out && eps && H > 0) memcpy(eps_out, eps, sizeof(double) * H * PE);
     fn_draws_finish(pl, draws, draws_out, stage);
-    for (int t = 0; t <= H; ++t) {
-        const double* row = &hstats[(size_t)t * Q];
-        memcpy(mean + (size_t)t * E, row, sizeof(double) * E);
-        memcpy(cov + (size_t)t * E * E, row + E, sizeof(double) * E * E);
-        if (t > 0 && reward_steps) reward_steps[t - 1] = row[Q - 1];
-    }
+    f.finish();
     return PILCO_OK;
 }

@@ -13,6 +13,8 @@
 //                    (step H - 1 meets lam_H = 0: its matrix is neither computed nor read)
 //   k_pg_param_partials   (t <= H - 2) per block of PT_BLOCK particles and per parameter the block's sum, added to the block's cell
 // and after the last group  k_pg_finish: the blocks' cells in block order, divided by P.
+// The host side of a call -- plan, buffers, staging, the sweep over the groups, the finish -- is ParticleGradFrame
+// (particle_frame.hip); the driver here passes it the forward launches of one step of a group.
 //
 // ORDER OF THE PARAMETER SUMS (no floating-point atomics): the particles are cut into blocks of PT_BLOCK = 128 consecutive
 // indices; one thread per quantity adds a block's particles of one step in index order (from zero) and adds that sum to the
@@ -23,7 +25,6 @@
 // environment, read at every call) the particles run in groups of a multiple of PT_BLOCK particles, each forward then reverse;
 // the particles are independent and a block never straddles two groups, so every output has the bits of the one-group run.
 #include "particles.h"
-#include "rbf_solve_adj.h"
 
 namespace pilco {
 
@@ -261,140 +262,70 @@ void launch_pg_finish(hipStream_t st, const double* part, double* out, int nblk,
 namespace {
 
 // Both entry points.  par: LinearController dW (U,E) | db (U); RbfController dbeta (U,bf) | dC (bf,E) | dl (U,E), over P.
+// The frame (particle_frame.hip) holds what surrounds the forward pass
 int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0,
                            int P, int H, const double* eps, unsigned long long seed, int observation_noise, double* reward,
                            double* reward_steps, std::vector<double>& par, double* dreturn_dx0) {
-    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
-    const int E = s.E, D = s.D, U = D - E;
-    const int bf = policy->kind == PILCO_POLICY_RBF ? ctx->slot[PILCO_SLOT_POLICY].N : 0;
-    const int Q = U > 0 ? pg_quantities(policy->kind, E, U, bf) : 0;
-    par.assign((size_t)Q, 0.0);
-    const size_t PE = (size_t)P * E;
+    ParticleGradFrame g(ctx, policy, rewards, n_rewards, x0, P, H, dreturn_dx0, par);
+    const int E = g.E, D = g.D;
+    const size_t PE = g.PE;
     if (H == 0) {
         *reward = 0.0;
         if (dreturn_dx0) std::fill(dreturn_dx0, dreturn_dx0 + PE, 0.0);
         return PILCO_OK;
     }
-    HIPCHK(hipSetDevice(ctx->device));
-    if (!s.factor_valid)
-        if (int r = pilco_gp_factorize(ctx, PILCO_SLOT_DYNAMICS)) return r;
-    if (!s.pred) s.pred = new PredictWork();
-    PredictWork& pw = *s.pred;
-    hipStream_t st = ctx->st;
+    ParticleTailArgs ta{};
+    if (int r = g.open((size_t)H * PE, ta.rw)) return r;
+    PredictWork& pw = *g.work;
+    hipStream_t st = g.st;
+    Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
     const PredictModel md = predict_model_of(s, 0, E);
-    const int npad = md.npad;
-    const int nblk = (P + PT_BLOCK - 1) / PT_BLOCK;
-    // the groups: a multiple of PT_BLOCK particles whose matrices fit the budget (at least one block)
-    const size_t per_particle = (size_t)(H - 1) * E * D;
-    int Pg = P;
-    if (per_particle * (size_t)P > pg_group_budget())
-        Pg = (int)std::min<size_t>((size_t)round_up(P, PT_BLOCK), std::max<size_t>(1, pg_group_budget() / per_particle / PT_BLOCK) * PT_BLOCK);
-    const int ldg = round_up(std::min(Pg, P), 64);
+    const int npad = md.npad, ldg = g.pl.ldg;
     const int ntc_max = std::min(ldg, predict_chunk_cap(E, npad));
-    std::vector<double> hp(particle_par_doubles(E, U), 0.0);
-    std::vector<double> hout((size_t)H + Q), hlam(dreturn_dx0 ? (size_t)E * ldg : 0);
     ENSURE(pw.Xt, (size_t)D * ntc_max);
     ENSURE(pw.Ks, (size_t)E * ntc_max * npad);
     ENSURE(pw.out, (size_t)2 * E * ntc_max);
     if (H > 1) {
         ENSURE(pw.jac, (size_t)2 * E * ntc_max * D);
         ENSURE(pw.jacW, (size_t)predict_jac_nops(md) * E * ntc_max * npad);
-        ENSURE(pw.pg_A, per_particle * ldg);
     }
-    ENSURE(pw.pt_x, (size_t)(H + 1) * PE);
-    ENSURE(pw.pt_eps, (size_t)H * PE);
-    ENSURE(pw.pt_rew, (size_t)P);
-    ENSURE(pw.pt_par, hp.size());
-    ENSURE(pw.pg_lam, (size_t)2 * E * ldg);
-    ENSURE(pw.pg_ds, (size_t)std::max(U, 1) * ldg);
-    ENSURE(pw.pg_part, (size_t)nblk * std::max(Q, 1));
-    ENSURE(pw.pg_rew, (size_t)H * nblk);
-    ENSURE(pw.pg_out, hout.size());
-
-    PgReverseArgs ra{};
-    ParticleTailArgs ta{};
-    size_t off = 0;
-    stage_policy(ctx, policy, hp, off, pw.pt_par.p, ra.pol);
-    ta.n_rewards = ra.n_rewards = n_rewards;
-    stage_rewards(rewards, n_rewards, E, hp, off, pw.pt_par.p, ta.rw);
-    for (int i = 0; i < n_rewards; ++i) ra.rw[i] = ta.rw[i];
-    ParticleHeadArgs ha = ra.pol;
-    StreamDrain drain{st};
-    // one upload: parameters, initial particles, the caller's draws
-    HIPCHK(hipMemcpyAsync(pw.pt_par.p, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(pw.pt_x.p, x0, sizeof(double) * PE, hipMemcpyHostToDevice, st));
-    if (eps) HIPCHK(hipMemcpyAsync(pw.pt_eps.p, eps, sizeof(double) * H * PE, hipMemcpyHostToDevice, st));
-    if (Q > 0) HIPCHK(hipMemsetAsync(pw.pg_part.p, 0, sizeof(double) * nblk * Q, st));
-
-    ta.E = E; ta.seed = seed;
+    if (int r = g.upload(eps)) return r;
+    ParticleHeadArgs& ha = g.ha;
+    ta.n_rewards = n_rewards; ta.E = E; ta.seed = seed;
     ta.noise = observation_noise ? s.noise.p : nullptr;
     ta.rew = pw.pt_rew.p;
     PgFoldArgs fa{};
     fa.noise = ta.noise; fa.ldg = ldg; fa.E = E; fa.D = D;
-    PgParamArgs pa{};
-    pa.ds = ra.ds = pw.pg_ds.p; pa.part = pw.pg_part.p; pa.ldg = ra.ldg = ldg; pa.Q = Q;
-    auto slab = [&](int t) { return pw.pt_x.p + (size_t)t * PE; };
-    for (int g0 = 0; g0 < P; g0 += Pg) {
-        const int ng = std::min(Pg, P - g0), nbg = (ng + PT_BLOCK - 1) / PT_BLOCK;
-        for (int t = 0; t < H; ++t) {
-            const bool jac = t < H - 1;
-            double* eps_t = pw.pt_eps.p + (size_t)t * PE;
-            ha.x = ta.x = slab(t);
-            ta.xn = slab(t + 1);
-            ta.t = t;
-            ta.eps_in = eps ? eps_t : nullptr;
-            ta.eps_out = eps ? nullptr : eps_t;
-            for (int l0 = 0; l0 < ng; l0 += ntc_max) {
-                const int p0 = g0 + l0, ntc = std::min(ntc_max, ng - l0), ldt = round_up(ntc, 64);
-                double *out_mean = pw.out.p, *out_var = pw.out.p + (size_t)E * ldt;
-                ha.Xt = pw.Xt.p; ha.p0 = p0; ha.ntc = ntc; ha.ldt = ldt;
-                launch_particle_head(st, ha);
-                if (int r = predict_points_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, out_mean, out_var)) return r;
-                ta.mu = out_mean; ta.var = out_var; ta.p0 = p0; ta.ntc = ntc; ta.ldt = ldt;
-                launch_particle_tail(st, ta);
-                if (!jac) continue;
-                double *dm = pw.jac.p, *dv = pw.jac.p + (size_t)E * ldt * D;
-                if (int r = predict_points_jac_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, pw.jacW.p, dm, dv)) return r;
-                fa.dmean = dm; fa.dvar = dv; fa.var = out_var; fa.eps = eps_t;
-                fa.A = pw.pg_A.p + (size_t)t * E * D * ldg;
-                fa.p0 = p0; fa.l0 = l0; fa.ntc = ntc; fa.ldt = ldt;
-                hipLaunchKernelGGL(k_pg_fold, dim3((ntc + 255) / 256, E), dim3(256), 0, st, fa);
-            }
-            launch_pg_reward_partials(st, pw.pt_rew.p, pw.pg_rew.p, P, g0 / PT_BLOCK, nbg, t, H);
+    auto step = [&](int g0, int ng, int t) {
+        const bool jac = t < H - 1;
+        double* eps_t = pw.pt_eps.p + (size_t)t * PE;
+        ha.x = ta.x = g.slab(t);
+        ta.xn = g.slab(t + 1);
+        ta.t = t;
+        ta.eps_in = eps ? eps_t : nullptr;
+        ta.eps_out = eps ? nullptr : eps_t;
+        for (int l0 = 0; l0 < ng; l0 += ntc_max) {
+            const int p0 = g0 + l0, ntc = std::min(ntc_max, ng - l0), ldt = round_up(ntc, 64);
+            double *out_mean = pw.out.p, *out_var = pw.out.p + (size_t)E * ldt;
+            ha.Xt = pw.Xt.p; ha.p0 = p0; ha.ntc = ntc; ha.ldt = ldt;
+            launch_particle_head(st, ha);
+            if (int r = predict_points_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, out_mean, out_var)) return r;
+            ta.mu = out_mean; ta.var = out_var; ta.p0 = p0; ta.ntc = ntc; ta.ldt = ldt;
+            launch_particle_tail(st, ta);
+            if (!jac) continue;
+            double *dm = pw.jac.p, *dv = pw.jac.p + (size_t)E * ldt * D;
+            if (int r = predict_points_jac_device(ctx, md, pw.Xt.p, ntc, ldt, pw.Ks.p, pw.jacW.p, dm, dv)) return r;
+            fa.dmean = dm; fa.dvar = dv; fa.var = out_var; fa.eps = eps_t;
+            fa.A = pw.pg_A.p + (size_t)t * E * D * ldg;
+            fa.p0 = p0; fa.l0 = l0; fa.ntc = ntc; fa.ldt = ldt;
+            hipLaunchKernelGGL(k_pg_fold, dim3((ntc + 255) / 256, E), dim3(256), 0, st, fa);
         }
-        ra.pol.p0 = g0; ra.pol.ntc = ng;
-        for (int t = H - 1; t >= 0; --t) {
-            const int in = (H - 1 - t) & 1;
-            ra.pol.x = slab(t);
-            ra.A = t < H - 1 ? pw.pg_A.p + (size_t)t * E * D * ldg : nullptr;
-            ra.lam_in = pw.pg_lam.p + (size_t)in * E * ldg;
-            ra.lam_out = pw.pg_lam.p + (size_t)(in ^ 1) * E * ldg;
-            launch_pg_reverse(st, ra);
-            if (Q > 0 && t < H - 1) {
-                pa.pol = ra.pol;
-                launch_pg_param_partials(st, pa);
-            }
-        }
-        HIPCHK(hipGetLastError());
-        if (dreturn_dx0) {   // lam_0, [E][ldg]: the group's download and synchronisation
-            const double* lam0 = pw.pg_lam.p + (size_t)(H & 1) * E * ldg;
-            HIPCHK(hipMemcpyAsync(hlam.data(), lam0, sizeof(double) * E * ldg, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            for (int l = 0; l < ng; ++l)
-                for (int e = 0; e < E; ++e) dreturn_dx0[(size_t)(g0 + l) * E + e] = hlam[(size_t)e * ldg + l];
-        }
-    }
-    // the rewards of the steps as k_particle_finish has them, and the parameter sums: one download, one synchronisation
-    launch_pg_finish(st, pw.pg_rew.p, pw.pg_out.p, nblk, H, P);
-    if (Q > 0) launch_pg_finish(st, pw.pg_part.p, pw.pg_out.p + H, nblk, Q, P);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hout.data(), pw.pg_out.p, sizeof(double) * hout.size(), hipMemcpyDeviceToHost, st));
+        return (int)PILCO_OK;
+    };
+    if (int r = g.sweep(step)) return r;
+    if (int r = g.finish_enqueue()) return r;
     HIPCHK(hipStreamSynchronize(st));
-    double total = 0.0;
-    for (int t = 0; t < H; ++t) total += hout[t];   // J: the steps' rewards added in step order
-    *reward = total;
-    if (reward_steps) memcpy(reward_steps, hout.data(), sizeof(double) * H);
-    std::copy(hout.begin() + H, hout.end(), par.begin());
+    g.finish(reward, reward_steps, par);
     return PILCO_OK;
 }
 
@@ -418,17 +349,10 @@ extern "C" int pilco_rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* 
                                             double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
     if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, false)) return r;
-    if (policy->kind == PILCO_POLICY_LINEAR && (!dW || !db)) return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad: null dW or db");
-    std::vector<double> par;
-    if (int r = rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
-                                       dreturn_dx0))
-        return r;
-    if (policy->kind == PILCO_POLICY_LINEAR) {
-        const size_t UE = (size_t)policy->control_dim * policy->state_dim;
-        memcpy(dW, par.data(), sizeof(double) * UE);
-        memcpy(db, par.data() + UE, sizeof(double) * policy->control_dim);
-    }
-    return PILCO_OK;
+    return pg_linear_entry(ctx, "rollout_particles_grad", policy, dW, db, [&](std::vector<double>& par) {
+        return rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
+                                      dreturn_dx0);
+    });
 }
 
 extern "C" int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards,
@@ -438,19 +362,8 @@ extern "C" int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_poli
                                                 double* dX, double* dY, double* dls, double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
     if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, true)) return r;
-    if (!Xp || !Yp || !lsp || !noisep || !dX || !dY || !dls)
-        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad_rbf: null policy parameters or null dX, dY or dls");
-    if (bf != ctx->slot[PILCO_SLOT_POLICY].N)
-        return fail(ctx, PILCO_E_SHAPE, "rollout_particles_grad_rbf: bf is not the number of points of the policy slot");
-    const int E = policy->state_dim, U = policy->control_dim;
-    if (!rbf_solve_adjoint(bf, E, U, Xp, Yp, lsp, noisep, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
-        return fail(ctx, PILCO_E_NOT_PD, "rollout_particles_grad_rbf: K + noise I of the policy is singular");
-    std::vector<double> par;
-    if (int r = rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
-                                       dreturn_dx0))
-        return r;
-    // dbeta (U,bf) | dC (bf,E) | dl (U,E): dbeta through beta_k = (K_k + noise_k I)^-1 Y_k into dY, dX and dls
-    const double *dbeta = par.data(), *dC = dbeta + (size_t)U * bf, *dl = dC + (size_t)bf * E;
-    rbf_solve_adjoint(bf, E, U, Xp, Yp, lsp, noisep, dC, dl, dbeta, dX, dY, dls);
-    return PILCO_OK;
+    return pg_rbf_entry(ctx, "rollout_particles_grad", policy, Xp, Yp, lsp, noisep, bf, dX, dY, dls, [&](std::vector<double>& par) {
+        return rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
+                                      dreturn_dx0);
+    });
 }

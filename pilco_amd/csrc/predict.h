@@ -6,9 +6,15 @@
 constexpr size_t PP_KS_BUDGET = size_t(1) << 24;   // doubles of cross-covariance per chunk (128 MB)
 
 // the per-call buffers of the predictions, and the FITC operands of per-output inducing inputs (a slot of its own whose
-// data, targets and hyper-parameters are views of the parent slot's); pt_*: the particle rollout's buffers (particles.hip),
-// pt_ev_*: its events' integers (first hits, block counts, counts) in buffers of doubles; pg_*: the buffers of the
-// particle gradient (particles_grad.hip); fn_*: the features, weights, residuals and V of the function-sample rollout
+// data, targets and hyper-parameters are views of the parent slot's).  Who reserves what for the particle entry points
+// (particle_frame.hip, docs/particle_frame.md):
+//   ParticleFrame::open       pt_x, pt_eps, pt_part, pt_stats, pt_par, pt_ev_* (the events' integers -- first hits, block
+//                             counts, counts -- in buffers of doubles)
+//   ParticleGradFrame::open   pt_x, pt_eps, pt_rew, pt_par, pg_*
+//   the marginal drivers      Xt, Ks, out, pt_rew (forward); Xt, Ks, out, jac, jacW (gradient)
+//   fn_setup                  fn_* (features, weights, residuals, V); the function drivers: Xt, pt_rew (forward)
+//   the conditioned driver    Ks, out, pc2_*
+//   pilco_debug_particle_actions   pt_x, Xt, pt_par
 struct PredictWork {
     DevBuf raw, Xt, Ks, out, jac, jacW;
     Slot fitc;
