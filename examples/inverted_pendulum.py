@@ -85,14 +85,18 @@ def initial_data(seed, J, T):
     return env, X, Y
 
 
-def run_hip(J=5, T=40, iters=3, maxiter=50, rollout_steps=100, seed=0, verbose=True):
-    """The loop on the HIP path.  -> dict of stage timings."""
-    from pilco_amd.controllers import RbfController
+def run_hip(J=5, T=40, iters=3, maxiter=50, rollout_steps=100, seed=0, verbose=True, mlp=False):
+    """The loop on the HIP path.  -> dict of stage timings.  mlp: a neural-network policy (MlpController, 32 tanh units) trained
+    on the particle return (docs/particle_mlp.md) in place of the RbfController trained on the moment-matched reward."""
+    from pilco_amd.controllers import MlpController, RbfController
     from pilco_amd.models import PILCO
     np.random.seed(seed)
     env, X, Y = initial_data(seed, J, T)
     state_dim, control_dim = Y.shape[1], X.shape[1] - Y.shape[1]
-    controller = RbfController(state_dim=state_dim, control_dim=control_dim, num_basis_functions=10, max_action=3.0)
+    if mlp:
+        controller = MlpController(state_dim=state_dim, control_dim=control_dim, num_hidden=32, max_action=3.0)
+    else:
+        controller = RbfController(state_dim=state_dim, control_dim=control_dim, num_basis_functions=10, max_action=3.0)
     pilco = PILCO((X, Y), controller=controller, horizon=40)     # examples/inverted_pendulum.py:24-27: defaults otherwise
     stages = []
     # one-time cost of the process, not of the loop: HIP runtime start-up, code objects of the library, the context's buffers
@@ -105,7 +109,7 @@ def run_hip(J=5, T=40, iters=3, maxiter=50, rollout_steps=100, seed=0, verbose=T
         t0 = time.perf_counter()
         pilco.optimize_models(verbose=False)
         t1 = time.perf_counter()
-        r = pilco.optimize_policy(maxiter=maxiter, restarts=1, verbose=False)
+        r = pilco.optimize_policy(maxiter=maxiter, restarts=1, verbose=False, objective="particles" if mlp else "moment_matching")
         t2 = time.perf_counter()
         X_new, Y_new, ret = rollout(env, lambda x: pilco.compute_action(x[None, :]), rollout_steps)
         X, Y = np.vstack((X, X_new)), np.vstack((Y, Y_new))
@@ -148,9 +152,10 @@ def main():
     ap.add_argument("--quick", action="store_true", help="short smoke variant (2 x 20 random steps, 1 iteration, maxiter 3)")
     ap.add_argument("--cpu", action="store_true", help="also run the CPU stand-in (oracle/cpu_loop.py)")
     ap.add_argument("--cpu-iters", type=int, default=None)
+    ap.add_argument("--mlp", action="store_true", help="HIP path: an MlpController trained on the particle return")
     args = ap.parse_args()
     kw = dict(J=2, T=20, iters=1, maxiter=3, rollout_steps=20) if args.quick else {}
-    res = run_hip(**kw)
+    res = run_hip(mlp=args.mlp, **kw)
     print("HIP path: total wall-clock %.2f s (+ %.2f s one-time runtime / library start-up before the loop)" % (res["total_s"], res["init_s"]))
     if args.cpu:
         kc = dict(kw)

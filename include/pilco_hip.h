@@ -148,7 +148,9 @@ int pilco_gp_sample_points(pilco_ctx* ctx, int slot, const double* Xs, int Nt, i
 typedef enum pilco_policy_kind {
     PILCO_POLICY_NONE = 0,   /* control_dim == 0 */
     PILCO_POLICY_LINEAR = 1, /* LinearController (pilco/controllers.py:39-63) */
-    PILCO_POLICY_RBF = 2     /* RbfController (pilco/controllers.py:80-129); GP in PILCO_SLOT_POLICY */
+    PILCO_POLICY_RBF = 2,    /* RbfController (pilco/controllers.py:80-129); GP in PILCO_SLOT_POLICY */
+    PILCO_POLICY_MLP = 3     /* one-hidden-layer tanh network (extension; docs/particle_mlp.md): particle entry points only; its
+                                parameters live in the context (pilco_set_policy_mlp), W and b stay NULL */
 } pilco_policy_kind;
 
 typedef struct pilco_policy {
@@ -275,6 +277,32 @@ int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_policy* policy,
                                      int observation_noise, const double* Xp, const double* Yp, const double* lsp,
                                      const double* noisep, int bf, double* reward, double* reward_steps, double* dX, double* dY,
                                      double* dls, double* dreturn_dx0);
+/* A neural-network policy for the particle entry points (extension; docs/particle_mlp.md): one hidden layer of `hidden` tanh
+ * units, x the state (E), j < hidden, k < U,
+ *   a_j = b1_j + sum_e W1_je x_e,   h_j = tanh(a_j),   s_k = b2_k + sum_j W2_kj h_j,   u_k = squash ? max_action_k sin(s_k) : s_k
+ * (the squash of the LinearController on particles: zero covariance, no exp(-0.5e-6) factor).  Every kernel evaluates the sums
+ * in one order: a_j by fma over e ascending from 0, then + b1_j; s_k by fma over j ascending from 0, then + b2_k.
+ * pilco_set_policy_mlp copies W1 (hidden,E), b1 (hidden), W2 (U,hidden), b2 (U) into the context on the host (no device call);
+ * a pilco_policy of kind PILCO_POLICY_MLP (W, b NULL; max_action, squash, state_dim, control_dim as for the linear kind) then
+ * acts with them in pilco_rollout_particles, _events, _fn, _cond and pilco_debug_particle_actions: the parameters travel in the
+ * call's one parameter upload.  PILCO_E_SHAPE for hidden outside 1..PILCO_MAX_MLP_HIDDEN, state_dim or control_dim < 1 or
+ * state_dim + control_dim > 32, or a null pointer: the context keeps what it had.  A particle entry point refuses kind 3 with
+ * PILCO_E_STATE when no network is set and with PILCO_E_SHAPE when the network's dimensions are not the dynamics slot's, before
+ * any launch or upload.  The moment-matching entry points (pilco_rollout*, pilco_propagate, pilco_policy_action) refuse kind 3:
+ * a network has no closed-form action moments. */
+#define PILCO_MAX_MLP_HIDDEN 256
+int pilco_set_policy_mlp(pilco_ctx* ctx, int state_dim, int control_dim, int hidden, const double* W1, const double* b1,
+                         const double* W2, const double* b2);
+/* pilco_rollout_particles_grad for the network of pilco_set_policy_mlp: dW1 (hidden,E), db1 (hidden), dW2 (U,hidden), db2 (U)
+ * in place of dW, db; everything else (reward, reward_steps, dreturn_dx0, eps, seed, observation_noise, the order of the sums,
+ * the groups) as there.  With ds_k = g_u[k] (squash ? max_action_k cos(s_k) : 1) and delta_j = (1 - h_j^2) sum_k W2_kj ds_k:
+ * dW1_je = sum_p delta_pj x_pe, db1_j = sum_p delta_pj, dW2_kj = sum_p ds_pk h_pj, db2_k = sum_p ds_pk, over P.  Refuses what
+ * pilco_rollout_particles_grad refuses, a policy kind other than MLP, and a null dW1, db1, dW2 or db2 -- all before any launch
+ * or upload, the outputs untouched.  pilco_rollout_particles_grad / _grad_rbf refuse kind 3. */
+int pilco_rollout_particles_grad_mlp(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                     const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                     int observation_noise, double* reward, double* reward_steps, double* dW1, double* db1,
+                                     double* dW2, double* db2, double* dreturn_dx0);
 /* Particle rollout on posterior FUNCTION samples (extension; docs/particle_functions.md).  pilco_rollout_particles moves a
  * particle by an independent marginal draw per step; here particle p draws ONE dynamics function f_p from the GP posterior
  * (pathwise conditioning on a random-Fourier-feature prior with L features, exact GP only) and rolls it out
@@ -332,6 +360,12 @@ int pilco_rollout_particles_fn_grad_rbf(pilco_ctx* ctx, const pilco_policy* poli
                                         const pilco_function_draws_out* draws_out, const double* Xp, const double* Yp,
                                         const double* lsp, const double* noisep, int bf, double* reward, double* reward_steps,
                                         double* dX, double* dY, double* dls, double* dreturn_dx0);
+/* The same for the network of pilco_set_policy_mlp; the gradient arguments are those of pilco_rollout_particles_grad_mlp. */
+int pilco_rollout_particles_fn_grad_mlp(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
+                                        const double* x0, int P, int H, const double* eps, unsigned long long seed,
+                                        int observation_noise, const pilco_function_draws* draws,
+                                        const pilco_function_draws_out* draws_out, double* reward, double* reward_steps,
+                                        double* dW1, double* db1, double* dW2, double* db2, double* dreturn_dx0);
 /* Particle rollout CONDITIONED ON ITS OWN PATH (extension; docs/particle_conditioned.md): exact and consistent along a
  * trajectory, for the exact GP and for FITC on the slot's shared inducing inputs.  The increments f(xt_0), .., f(xt_{H-1}) of a
  * particle (xt = [x, u]) are jointly Gaussian under the posterior; step t is drawn conditioned on the particle's own earlier

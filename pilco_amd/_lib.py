@@ -18,7 +18,8 @@ PILCO_OK = 0
 STATUS_NAMES = {1: "PILCO_E_SHAPE", 2: "PILCO_E_NOT_PD", 3: "PILCO_E_HIP", 4: "PILCO_E_RCCL",
                 5: "PILCO_E_STATE", 6: "PILCO_E_ALLOC"}
 SLOT_DYNAMICS, SLOT_POLICY = 0, 1
-POLICY_NONE, POLICY_LINEAR, POLICY_RBF = 0, 1, 2
+POLICY_NONE, POLICY_LINEAR, POLICY_RBF, POLICY_MLP = 0, 1, 2, 3
+MAX_MLP_HIDDEN = 256   # PILCO_MAX_MLP_HIDDEN
 REWARD_EXPONENTIAL, REWARD_LINEAR = 1, 2
 MAX_EVENTS, MAX_EVENT_CLAUSES = 8, 4
 COMM_ID_BYTES = 128
@@ -150,6 +151,12 @@ SIGNATURES = {
                                              C.POINTER(FunctionDraws), C.POINTER(FunctionDrawsOut)]),
     "pilco_rollout_particles_grad": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
                                                _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_set_policy_mlp": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles_grad_mlp": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
+                                                   _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pilco_rollout_particles_fn_grad_mlp": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int,
+                                                      C.c_int, _dp, C.c_ulonglong, C.c_int, C.POINTER(FunctionDraws),
+                                                      C.POINTER(FunctionDrawsOut), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pilco_rollout_particles_grad_rbf": (C.c_int, [_vp, C.POINTER(PolicyStruct), C.POINTER(RewardTerm), C.c_int, _dp, C.c_int, C.c_int,
                                                    _dp, C.c_ulonglong, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
                                                    _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -707,6 +714,55 @@ class Context:
         dx0 = np.empty((P, E)) if want_dx0 else None
         self._chk(self.lib.pilco_rollout_particles_grad(*head, _ptr(rew), _ptr(steps), _ptr(dW), _ptr(db), _ptr(dx0)))
         return float(rew[0]), steps, dW, db, dx0
+
+    def set_policy_mlp(self, W1, b1, W2, b2):
+        """The network a policy of kind POLICY_MLP acts with on the particle entry points (pilco_set_policy_mlp;
+        docs/particle_mlp.md): W1 (hidden, E), b1 (hidden,), W2 (U, hidden), b2 (U,), copied into the context on the host."""
+        W1 = _f64(W1)
+        if W1.ndim != 2:
+            raise ValueError("set_policy_mlp: W1 must be (hidden, state_dim)")
+        Hn, E = W1.shape
+        W2 = _f64(W2)
+        if W2.ndim != 2 or W2.shape[1] != Hn:
+            raise ValueError(f"set_policy_mlp: W2 must be (control_dim, {Hn})")
+        U = W2.shape[0]
+        b1, b2 = _f64(b1, (Hn,)), _f64(b2, (U,))
+        self._chk(self.lib.pilco_set_policy_mlp(self.h, E, U, Hn, _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2)))
+        self._mlp_hidden = Hn
+        self._mlp_set = tuple(np.array(a) for a in (W1, b1, W2, b2))
+
+    @property
+    def policy_mlp_set(self):
+        """The parameters (W1, b1, W2, b2) of the last set_policy_mlp, or None."""
+        return getattr(self, "_mlp_set", None)
+
+    def _mlp_grad_arrays(self, policy):
+        E, U, Hn = policy["state_dim"], policy["control_dim"], int(getattr(self, "_mlp_hidden", 0))
+        return np.zeros((Hn, E)), np.zeros((Hn,)), np.zeros((U, Hn)), np.zeros((U,))
+
+    def rollout_particles_grad_mlp(self, policy, rewards, x0, H, eps=None, seed=0, observation_noise=False, want_dx0=False):
+        """The same for the network of set_policy_mlp (pilco_rollout_particles_grad_mlp): (reward, reward_steps, dW1 (hidden, E),
+        db1 (hidden,), dW2 (U, hidden), db2 (U,), dreturn_dx0 or None)."""
+        head, keep, P, H = self._particle_grad_args(policy, rewards, x0, H, eps, seed, observation_noise)
+        rew = np.zeros((1,)); steps = np.empty((max(H, 0),))
+        dW1, db1, dW2, db2 = self._mlp_grad_arrays(policy)
+        dx0 = np.empty((P, policy["state_dim"])) if want_dx0 else None
+        self._chk(self.lib.pilco_rollout_particles_grad_mlp(*head, _ptr(rew), _ptr(steps), _ptr(dW1), _ptr(db1), _ptr(dW2), _ptr(db2),
+                                                            _ptr(dx0)))
+        return float(rew[0]), steps, dW1, db1, dW2, db2, dx0
+
+    def rollout_particles_fn_grad_mlp(self, policy, rewards, x0, H, num_features=512, function_draws=None, eps=None, seed=0,
+                                      observation_noise=False, want_dx0=False, want_draws=False):
+        """rollout_particles_fn_grad for the network of set_policy_mlp (pilco_rollout_particles_fn_grad_mlp): (reward,
+        reward_steps, dW1, db1, dW2, db2, dreturn_dx0 or None, draws or None)."""
+        head, keep, P, H = self._particle_grad_args(policy, rewards, x0, H, eps, seed, observation_noise)
+        d, do, out, keep2 = self._function_draws(policy, P, num_features, function_draws, want_draws)
+        rew = np.zeros((1,)); steps = np.empty((max(H, 0),))
+        dW1, db1, dW2, db2 = self._mlp_grad_arrays(policy)
+        dx0 = np.empty((P, policy["state_dim"])) if want_dx0 else None
+        self._chk(self.lib.pilco_rollout_particles_fn_grad_mlp(*head, C.byref(d), C.byref(do) if do is not None else None, _ptr(rew),
+                                                               _ptr(steps), _ptr(dW1), _ptr(db1), _ptr(dW2), _ptr(db2), _ptr(dx0)))
+        return float(rew[0]), steps, dW1, db1, dW2, db2, dx0, out
 
     def rollout_particles_grad_rbf(self, policy, rewards, x0, H, Xp, Yp, lsp, noisep, eps=None, seed=0, observation_noise=False,
                                    want_dx0=False):

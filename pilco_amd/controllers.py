@@ -221,3 +221,80 @@ class RbfController:
     def trainable_parameters(self):
         """Centres, targets and per-output lengthscales -- the reference's trainable set (controllers.py:70-73,100)."""
         return [p for p in [self.centres, self.targets] + [m.kernel.lengthscales for m in self.models] if p.trainable]
+
+
+class MlpController:
+    """Extension (docs/particle_mlp.md): a neural-network policy for the PARTICLE paths -- one hidden layer of tanh units,
+
+        h = tanh(W1 x + b1),   s = W2 h + b2,   u = max_action * sin(s)  (squash)  or  s.
+
+    A network has no closed-form action moments: sample_trajectories, particle_value_and_gradient and
+    optimize_policy(objective="particles") work with it, the moment-matching methods raise NotImplementedError.  The
+    parameters travel to the device with every particle call (Context.set_policy_mlp keeps the host copy)."""
+
+    def __init__(self, state_dim, control_dim, num_hidden=32, max_action=1.0, ctx=None):
+        if not 1 <= int(num_hidden) <= _lib.MAX_MLP_HIDDEN:
+            raise ValueError("MlpController: num_hidden must be 1..%d" % _lib.MAX_MLP_HIDDEN)
+        self.state_dim = state_dim
+        self.control_dim = control_dim
+        self.num_hidden = int(num_hidden)
+        self.W1 = Parameter(np.zeros((self.num_hidden, state_dim)), name="W1")
+        self.b1 = Parameter(np.zeros((self.num_hidden,)), name="b1")
+        self.W2 = Parameter(np.zeros((control_dim, self.num_hidden)), name="W2")
+        self.b2 = Parameter(np.zeros((1, control_dim)), name="b2")
+        self.max_action = max_action
+        self._ctx = ctx
+        self.randomize()
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = _lib.resolve_ctx(self)
+        return self._ctx
+
+    def _host(self):
+        return (np.asarray(self.W1.numpy(), np.float64), np.asarray(self.b1.numpy(), np.float64).reshape(-1),
+                np.asarray(self.W2.numpy(), np.float64), np.asarray(self.b2.numpy(), np.float64).reshape(-1))
+
+    def _scale(self):
+        return np.broadcast_to(np.asarray(self.max_action, np.float64).reshape(-1), (self.control_dim,))
+
+    def policy_spec(self, squash=True):
+        par = self._host()
+        ctx = self.ctx
+        sent = ctx.policy_mlp_set   # a context holds ONE network: another controller may have set its own since
+        if sent is None or any(a.shape != b.shape or not np.array_equal(a, b) for a, b in zip(par, sent)):
+            ctx.set_policy_mlp(*par)
+        return dict(kind=_lib.POLICY_MLP, state_dim=self.state_dim, control_dim=self.control_dim, max_action=self.max_action,
+                    squash=squash)
+
+    def compute_action(self, m, s, squash=True):
+        """The deterministic action at m (1, E), on the host: (M (1, U), zeros (U, U), zeros (E, U)).  Any non-zero s raises
+        NotImplementedError: the moments of a network's action under a Gaussian state have no closed form."""
+        if np.any(np.asarray(s, np.float64) != 0.0):
+            raise NotImplementedError("MlpController.compute_action: no action moments under a state covariance; an MlpController "
+                                      "serves the particle paths (optimize_policy(objective=\"particles\"), sample_trajectories)")
+        W1, b1, W2, b2 = self._host()
+        x = np.asarray(m, np.float64).reshape(-1)
+        a = W2 @ np.tanh(W1 @ x + b1) + b2
+        M = self._scale() * np.sin(a) if squash else a
+        return M.reshape(1, -1), np.zeros((self.control_dim, self.control_dim)), np.zeros((self.state_dim, self.control_dim))
+
+    def action_jacobian(self, x):
+        """d u / d x (U, E) of the deterministic action u = compute_action(x, 0)[0] at the state x (E,) (host NumPy)."""
+        W1, b1, W2, b2 = self._host()
+        x = np.asarray(x, np.float64).reshape(-1)
+        h = np.tanh(W1 @ x + b1)
+        a = W2 @ h + b2
+        return (self._scale() * np.cos(a))[:, None] * ((W2 * (1.0 - h * h)) @ W1)
+
+    def randomize(self):
+        """W1 ~ N(0, 1 / E), W2 ~ N(0, 1 / num_hidden), b1 = 0, b2 ~ N(0, 1), from NumPy's global generator in this order."""
+        self.W1.assign(np.random.normal(size=self.W1.shape) / np.sqrt(self.state_dim))
+        self.W2.assign(np.random.normal(size=self.W2.shape) / np.sqrt(self.num_hidden))
+        self.b1.assign(np.zeros(self.b1.shape))
+        self.b2.assign(np.random.normal(size=self.b2.shape))
+
+    @property
+    def trainable_parameters(self):
+        return [p for p in (self.W1, self.b1, self.W2, self.b2) if p.trainable]

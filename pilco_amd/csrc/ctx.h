@@ -186,6 +186,8 @@ struct pilco_ctx {
     // dynamics slot BORROWS this context's model buffers; owned and destroyed by this context
     std::vector<pilco_ctx*> lanes;
     bool is_lane = false;
+    // pilco_set_policy_mlp: the network of PILCO_POLICY_MLP on the host, W1 [Hn][E] | b1 [Hn] | W2 [U][Hn] | b2 [U]; Hn == 0: none set
+    struct MlpPolicy { int E = 0, U = 0, Hn = 0; std::vector<double> par; } mlp;
     int share_cu = 0;   // > 0 while this context runs as one of several lanes of a batch call (heads launch their two-per-CU build)
 };
 

@@ -14,7 +14,7 @@ int check_policy(pilco_ctx* ctx, const pilco_policy* policy) {
     const int E = s.E, D = s.D, U = D - E;
     if (policy->state_dim != E || policy->control_dim != U || U < 0 || D > MAX_D)
         return fail(ctx, PILCO_E_SHAPE, "rollout_particles: policy dims do not match the model (state_dim must be E, control_dim D-E)");
-    if (policy->kind < 0 || policy->kind > 2) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: unknown policy kind");
+    if (policy->kind < 0 || policy->kind > PILCO_POLICY_MLP) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: unknown policy kind");
     if (policy->kind == PILCO_POLICY_NONE && U != 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: policy NONE needs D == E");
     if (policy->kind != PILCO_POLICY_NONE && U == 0) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: a policy needs control_dim > 0");
     if (policy->kind == PILCO_POLICY_LINEAR && (!policy->W || !policy->b))
@@ -24,10 +24,15 @@ int check_policy(pilco_ctx* ctx, const pilco_policy* policy) {
         if (!ps.factor_valid || ps.M > 0) return fail(ctx, PILCO_E_STATE, "rollout_particles: RBF policy slot has no current (exact) factorisation");
         if (ps.D != E || ps.E != U) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: RBF policy GP must map state_dim -> control_dim");
     }
+    if (policy->kind == PILCO_POLICY_MLP) {
+        if (ctx->mlp.Hn == 0) return fail(ctx, PILCO_E_STATE, "rollout_particles: MLP policy needs pilco_set_policy_mlp first");
+        if (ctx->mlp.E != E || ctx->mlp.U != U) return fail(ctx, PILCO_E_SHAPE, "rollout_particles: the MLP policy must map state_dim -> control_dim");
+    }
     return PILCO_OK;
 }
 
-// the policy's parameters into the staging vector hp (W[U*E] b[U] maxact[U]) and the action kernel's arguments; dev: where hp goes
+// the policy's parameters into the staging vector hp (W[U*E] b[U] maxact[U]; MLP policy: W1 b1 W2 b2 maxact[U]) and the action
+// kernel's arguments; dev: where hp goes
 void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double>& hp, size_t& off, const double* dev,
                   ParticleHeadArgs& ha) {
     const Slot &s = ctx->slot[PILCO_SLOT_DYNAMICS], &ps = ctx->slot[PILCO_SLOT_POLICY];
@@ -38,6 +43,13 @@ void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double
         ha.W = dev + off; off += (size_t)U * E;
         memcpy(&hp[off], policy->b, sizeof(double) * U);
         ha.b = dev + off; off += U;
+    }
+    if (policy->kind == PILCO_POLICY_MLP) {
+        const int Hn = ctx->mlp.Hn;
+        std::copy(ctx->mlp.par.begin(), ctx->mlp.par.end(), hp.begin() + off);
+        ha.Hn = Hn;
+        ha.W1 = dev + off; ha.b1 = ha.W1 + (size_t)Hn * E; ha.W2 = ha.b1 + Hn; ha.b2 = ha.W2 + (size_t)U * Hn;
+        off += ctx->mlp.par.size();
     }
     for (int u = 0; u < U; ++u) hp[off + u] = policy->max_action ? policy->max_action[u] : 1.0;
     ha.maxact = dev + off; off += U;
@@ -122,7 +134,7 @@ int ParticleFrame::open(int nslab_, size_t eps_doubles_, ParticleReward* rw) {
     if (int r = particle_work(ctx, work)) return r;
     PredictWork& pw = *work;
     const int P = c.P, H = c.H;
-    hp.assign(particle_par_doubles(E, U), 0.0);
+    hp.assign(particle_par_doubles(E, U, policy_mlp_hidden(ctx, c.policy)), 0.0);
     hstats.resize((size_t)(H + 1) * Q);
     ENSURE(pw.pt_x, (size_t)nslab * PE);
     if (eps_doubles) ENSURE(pw.pt_eps, eps_doubles);
@@ -210,7 +222,7 @@ ParticleGradFrame::ParticleGradFrame(pilco_ctx* ctx_, const pilco_policy* policy
     : ctx(ctx_), policy(policy_), rewards(rewards_), n_rewards(n_rewards_), x0(x0_), P(P_), H(H_), dreturn_dx0(dreturn_dx0_) {
     const Slot& s = ctx->slot[PILCO_SLOT_DYNAMICS];
     E = s.E; D = s.D; U = D - E;
-    const int bf = policy->kind == PILCO_POLICY_RBF ? ctx->slot[PILCO_SLOT_POLICY].N : 0;
+    const int bf = policy->kind == PILCO_POLICY_RBF ? ctx->slot[PILCO_SLOT_POLICY].N : policy_mlp_hidden(ctx, policy);
     Q = U > 0 ? pg_quantities(policy->kind, E, U, bf) : 0;
     PE = (size_t)P * E;
     par.assign((size_t)Q, 0.0);
@@ -222,7 +234,7 @@ int ParticleGradFrame::open(size_t eps_doubles, ParticleReward* rw) {
     PredictWork& pw = *work;
     pl = pg_plan(P, H, E, D, pg_group_budget());
     const int ldg = pl.ldg, nblk = pl.nblk;
-    hp.assign(particle_par_doubles(E, U), 0.0);
+    hp.assign(particle_par_doubles(E, U, policy_mlp_hidden(ctx, policy)), 0.0);
     hout.resize((size_t)H + Q);
     hlam.resize(dreturn_dx0 ? (size_t)E * ldg : 0);
     if (H > 1) ENSURE(pw.pg_A, pl.per_particle * ldg);
@@ -316,6 +328,41 @@ int pg_linear_entry(pilco_ctx* ctx, const char* who, const pilco_policy* policy,
         memcpy(dW, par.data(), sizeof(double) * UE);
         memcpy(db, par.data() + UE, sizeof(double) * policy->control_dim);
     }
+    return PILCO_OK;
+}
+
+int pg_mlp_entry(pilco_ctx* ctx, const char* who, const pilco_policy* policy, double* dW1, double* db1, double* dW2, double* db2,
+                 const PgRollout& rollout) {
+    if (!dW1 || !db1 || !dW2 || !db2) return fail(ctx, PILCO_E_SHAPE, std::string(who) + "_mlp: null dW1, db1, dW2 or db2");
+    std::vector<double> par;
+    if (int r = rollout(par)) return r;
+    // dW1 (Hn,E) | db1 (Hn) | dW2 (U,Hn) | db2 (U)
+    const size_t Hn = (size_t)ctx->mlp.Hn, E = (size_t)policy->state_dim, U = (size_t)policy->control_dim;
+    const double* q = par.data();
+    memcpy(dW1, q, sizeof(double) * Hn * E); q += Hn * E;
+    memcpy(db1, q, sizeof(double) * Hn); q += Hn;
+    memcpy(dW2, q, sizeof(double) * U * Hn); q += U * Hn;
+    memcpy(db2, q, sizeof(double) * U);
+    return PILCO_OK;
+}
+
+// the network of PILCO_POLICY_MLP: a host copy, staged into every call's parameter upload by stage_policy
+extern "C" int pilco_set_policy_mlp(pilco_ctx* ctx, int state_dim, int control_dim, int hidden, const double* W1, const double* b1,
+                                    const double* W2, const double* b2) {
+    if (!ctx) return PILCO_E_SHAPE;
+    if (hidden < 1 || hidden > PILCO_MAX_MLP_HIDDEN) return fail(ctx, PILCO_E_SHAPE, "set_policy_mlp: hidden must be 1..256");
+    if (state_dim < 1 || control_dim < 1 || state_dim + control_dim > MAX_D)
+        return fail(ctx, PILCO_E_SHAPE, "set_policy_mlp: state_dim and control_dim must be positive, their sum at most 32");
+    if (!W1 || !b1 || !W2 || !b2) return fail(ctx, PILCO_E_SHAPE, "set_policy_mlp: null W1, b1, W2 or b2");
+    const size_t E = (size_t)state_dim, U = (size_t)control_dim, Hn = (size_t)hidden;
+    std::vector<double> par(Hn * (E + 1) + U * (Hn + 1));
+    double* q = par.data();
+    memcpy(q, W1, sizeof(double) * Hn * E); q += Hn * E;
+    memcpy(q, b1, sizeof(double) * Hn); q += Hn;
+    memcpy(q, W2, sizeof(double) * U * Hn); q += U * Hn;
+    memcpy(q, b2, sizeof(double) * U);
+    ctx->mlp.par.swap(par);
+    ctx->mlp.E = state_dim; ctx->mlp.U = control_dim; ctx->mlp.Hn = hidden;
     return PILCO_OK;
 }
 

@@ -20,7 +20,51 @@ struct ParticleHeadArgs {
     const double *W, *b, *maxact;             // LinearController [U][E], [U]; scale of the squash [U]
     const double *pc, *pls, *pvar, *pbeta;    // RbfController (policy slot): centres [E][pnpad], lengthscales [U][E], variances [U], beta [U][pnpad]
     int pn, pnpad;
+    const double *W1, *b1, *W2, *b2;          // MLP policy (pilco_set_policy_mlp): [Hn][E], [Hn], [U][Hn], [U]
+    int Hn;
 };
+
+constexpr int HEAD_BLOCK = 256;   // particles (threads) per workgroup of k_particle_head
+// doubles of an MLP policy's parameters W1 [Hn][E] | b1 [Hn] | W2 [U][Hn] | b2 [U]: contiguous in the parameter upload from W1 on
+inline int mlp_par_doubles(int E, int U, int Hn) { return Hn * (E + 1) + U * (Hn + 1); }
+// dynamic LDS of k_particle_head: MLP policy [U][HEAD_BLOCK] the pre-squash sums, [E][HEAD_BLOCK] the states (a column per
+// thread), then the workgroup's copy of the parameters; none otherwise
+inline int particle_head_lds_doubles(int kind, int E, int U, int Hn) {
+    return kind == PILCO_POLICY_MLP ? (U + E) * HEAD_BLOCK + mlp_par_doubles(E, U, Hn) : 0;
+}
+
+// The MLP policy's hidden unit at a state (element e: x[e * stride]) from row j of W1 (w1 [E]) and b1_j, and its adjoint factor
+// from column j of W2 (element k: w2[k * ldw]), as EVERY kernel evaluates them (docs/particle_mlp.md): a_j by fma over e
+// ascending from 0, then + b1_j; h_j = tanh(a_j); delta_j = (1 - h_j^2) sum_k W2_kj ds_k, k ascending (ds element k:
+// ds[k * dstride]), 1 - h^2 as one fma.  The operands come from LDS: a dependent chain of loads from global memory per term
+// costs the kernels their time (docs/particle_mlp.md, "Measured times"); four terms' loads are issued before their fmas
+#if defined(__HIPCC__)
+__device__ __forceinline__ double mlp_hidden(const double* w1, double b1j, const double* x, int stride, int E) {
+    double acc = 0.0;
+    int e = 0;
+    for (; e + 4 <= E; e += 4) {
+        const double w0 = w1[e], wa = w1[e + 1], wb = w1[e + 2], wc = w1[e + 3];
+        const double x0 = x[e * stride], xa = x[(e + 1) * stride], xb = x[(e + 2) * stride], xc = x[(e + 3) * stride];
+        acc = fma(w0, x0, acc);
+        acc = fma(wa, xa, acc);
+        acc = fma(wb, xb, acc);
+        acc = fma(wc, xc, acc);
+    }
+    for (; e < E; ++e) acc = fma(w1[e], x[e * stride], acc);
+    acc += b1j;
+    return tanh(acc);
+}
+__device__ __forceinline__ double mlp_delta(const double* w2, int ldw, double h, const double* ds, int dstride, int U) {
+    double t = 0.0;
+    for (int k = 0; k < U; ++k) t = fma(w2[k * ldw], ds[k * dstride], t);
+    return fma(-h, h, 1.0) * t;
+}
+// the workgroup's copy of the parameters (before a barrier)
+__device__ __forceinline__ void mlp_stage(const ParticleHeadArgs& a, double* w, int tid, int nthreads) {
+    const int n = a.Hn * (a.E + 1) + a.U * (a.Hn + 1);
+    for (int q = tid; q < n; q += nthreads) w[q] = a.W1[q];
+}
+#endif
 
 struct ParticleReward {
     int kind;
@@ -99,8 +143,11 @@ struct PgReverseArgs {
     ParticleReward rw[MAX_REWARD_TERMS];
 };
 
-// dynamic LDS: [3 E + U][PG_RB] the particle's lam, x, lam' and g_u / ds (a column per thread), then 1 / lengthscale [U][E]
-inline int pg_reverse_lds_doubles(int E, int U) { return (3 * E + U) * PG_RB + U * E; }
+// dynamic LDS: [3 E + U][PG_RB] the particle's lam, x, lam' and g_u / ds (a column per thread), then 1 / lengthscale [U][E];
+// MLP policy: then [U][PG_RB] the pre-squash sums and the workgroup's copy of the parameters
+inline int pg_reverse_lds_doubles(int E, int U, int kind, int Hn) {
+    return (3 * E + U) * PG_RB + U * E + (kind == PILCO_POLICY_MLP ? U * PG_RB + mlp_par_doubles(E, U, Hn) : 0);
+}
 
 struct PgParamArgs {
     ParticleHeadArgs pol;   // as PgReverseArgs
@@ -109,8 +156,20 @@ struct PgParamArgs {
     int ldg, Q;
 };
 
-// quantities of a policy: LinearController dW [U][E] | db [U]; RbfController dbeta [U][bf] | dC [bf][E] | dl [U][E]
-inline int pg_quantities(int kind, int E, int U, int bf) { return kind == PILCO_POLICY_RBF ? U * bf + bf * E + U * E : U * E + U; }
+// quantities of a policy: LinearController dW [U][E] | db [U]; RbfController dbeta [U][bf] | dC [bf][E] | dl [U][E];
+// MLP policy (bf: its hidden units) dW1 [bf][E] | db1 [bf] | dW2 [U][bf] | db2 [U]
+inline int pg_quantities(int kind, int E, int U, int bf) {
+    if (kind == PILCO_POLICY_MLP) return bf * (E + 1) + U * (bf + 1);
+    return kind == PILCO_POLICY_RBF ? U * bf + bf * E + U * E : U * E + U;
+}
+
+// k_pg_param_partials, MLP policy: the block's h, then delta, in tiles of PG_MLP_TILE hidden units, [PT_BLOCK][PG_MLP_TILE + 1]
+// (dynamic LDS; the odd row length keeps a thread's row off its neighbours' banks), then the tile's parameters: rows of W1
+// [PG_MLP_TILE][E], b1 [PG_MLP_TILE], columns of W2 [U][PG_MLP_TILE]
+constexpr int PG_MLP_TILE = 64;
+inline int pg_param_lds_doubles(int kind, int E, int U) {
+    return kind == PILCO_POLICY_MLP ? PT_BLOCK * (PG_MLP_TILE + 1) + PG_MLP_TILE * (E + 1 + U) : 0;
+}
 
 }  // namespace pilco
 
@@ -124,8 +183,9 @@ void launch_pg_finish(hipStream_t st, const double* part, double* out, int nblk,
 // doubles of stored step matrices per group: PILCO_PARTICLE_GRAD_BUDGET, read at every call, or 2^27
 size_t pg_group_budget();
 // the refusals of the gradient entry points, before any launch or upload; who: the entry point without "pilco_" and "_rbf"
+// entry: the policy kind the entry point differentiates (PILCO_POLICY_LINEAR also takes no policy)
 int check_particle_grad_call(pilco_ctx* ctx, const char* who, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards,
-                             const double* x0, int P, int H, const double* reward, bool rbf);
+                             const double* x0, int P, int H, const double* reward, int entry);
 
 struct StreamDrain {   // the staging vectors of a call are locals: nothing of the stream may outlive them
     hipStream_t st;
@@ -145,8 +205,13 @@ int check_particle_state(pilco_ctx* ctx, int P, int H);
 int check_particle_terms(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards);
 // the policy against the dynamics slot (and, RbfController, the policy slot)
 int check_policy(pilco_ctx* ctx, const pilco_policy* policy);
-// doubles of the staging vector hp: W[U*E] b[U] maxact[U], then per reward W[E*E] t[E] (exponential) or W[E] (linear)
-inline size_t particle_par_doubles(int E, int U) { return (size_t)U * E + 2 * U + (size_t)MAX_REWARD_TERMS * (E * E + E) + 8; }
+// doubles of the staging vector hp: W[U*E] b[U] maxact[U], then per reward W[E*E] t[E] (exponential) or W[E] (linear); an MLP
+// policy of Hn hidden units (0: none) puts W1[Hn*E] b1[Hn] W2[U*Hn] b2[U] in the place of W, b
+inline size_t particle_par_doubles(int E, int U, int Hn) {
+    return (size_t)U * E + 2 * U + (size_t)MAX_REWARD_TERMS * (E * E + E) + 8 + (size_t)Hn * (E + 1) + (size_t)U * (Hn + 1);
+}
+// the hidden units of the policy's network (0 for every other kind)
+inline int policy_mlp_hidden(const pilco_ctx* ctx, const pilco_policy* policy) { return policy->kind == PILCO_POLICY_MLP ? ctx->mlp.Hn : 0; }
 // the policy's parameters into hp (from off on) and the action kernel's arguments; dev: where hp goes
 void stage_policy(pilco_ctx* ctx, const pilco_policy* policy, std::vector<double>& hp, size_t& off, const double* dev,
                   pilco::ParticleHeadArgs& ha);
@@ -257,5 +322,8 @@ struct ParticleGradFrame {
 // singularity probe, and dbeta | dC | dl through beta_k = (K_k + noise_k I)^-1 Y_k into dX, dY and dls
 using PgRollout = std::function<int(std::vector<double>& par)>;
 int pg_linear_entry(pilco_ctx* ctx, const char* who, const pilco_policy* policy, double* dW, double* db, const PgRollout& rollout);
+// MLP policy: the refusal of null dW1, db1, dW2, db2 and par = dW1 | db1 | dW2 | db2
+int pg_mlp_entry(pilco_ctx* ctx, const char* who, const pilco_policy* policy, double* dW1, double* db1, double* dW2, double* db2,
+                 const PgRollout& rollout);
 int pg_rbf_entry(pilco_ctx* ctx, const char* who, const pilco_policy* policy, const double* Xp, const double* Yp, const double* lsp,
                  const double* noisep, int bf, double* dX, double* dY, double* dls, const PgRollout& rollout);

@@ -27,11 +27,14 @@
 
 namespace pilco {
 
+static_assert(HEAD_BLOCK == 256, "k_particle_head: one thread per particle, 256 per workgroup");
 __global__ __launch_bounds__(256) void k_particle_head(ParticleHeadArgs a) {
+    extern __shared__ double head_lds[];   // MLP policy: [U][HEAD_BLOCK] the pre-squash sums, [E][HEAD_BLOCK] the states, the parameters
     const int E = a.E, U = a.U, ldt = a.ldt;
     __shared__ double il_s[MAX_D * MAX_D / 4];   // RbfController: 1 / lengthscale [U][E]  (U + E <= MAX_D)
     if (a.kind == PILCO_POLICY_RBF)
         for (int q = threadIdx.x; q < U * E; q += 256) il_s[q] = 1.0 / a.pls[q];
+    if (a.kind == PILCO_POLICY_MLP) mlp_stage(a, head_lds + (U + E) * HEAD_BLOCK, threadIdx.x, HEAD_BLOCK);
     __syncthreads();
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= ldt) return;
@@ -41,6 +44,23 @@ __global__ __launch_bounds__(256) void k_particle_head(ParticleHeadArgs a) {
     }
     const double* xr = a.x + (long)(a.p0 + i) * E;
     for (int e = 0; e < E; ++e) a.Xt[(long)e * ldt + i] = xr[e];
+    if (a.kind == PILCO_POLICY_MLP) {   // s_k by fma over j ascending, then + b2_k; the weights are wave-uniform LDS reads
+        const int Hn = a.Hn;
+        double* sc = head_lds + threadIdx.x;
+        double* xs = sc + U * HEAD_BLOCK;
+        const double *W1 = head_lds + (U + E) * HEAD_BLOCK, *b1 = W1 + Hn * E, *W2 = b1 + Hn, *b2 = W2 + U * Hn;
+        for (int e = 0; e < E; ++e) xs[e * HEAD_BLOCK] = xr[e];
+        for (int k = 0; k < U; ++k) sc[k * HEAD_BLOCK] = 0.0;
+        for (int j = 0; j < Hn; ++j) {
+            const double h = mlp_hidden(W1 + j * E, b1[j], xs, HEAD_BLOCK, E);
+            for (int k = 0; k < U; ++k) sc[k * HEAD_BLOCK] = fma(W2[k * Hn + j], h, sc[k * HEAD_BLOCK]);
+        }
+        for (int k = 0; k < U; ++k) {
+            const double s = sc[k * HEAD_BLOCK] + b2[k];
+            a.Xt[(long)(E + k) * ldt + i] = a.squash ? a.maxact[k] * sin(s) : s;
+        }
+        return;
+    }
     for (int k = 0; k < U; ++k) {
         double s = 0.0, scale = a.maxact[k];
         if (a.kind == PILCO_POLICY_LINEAR) {
@@ -170,7 +190,8 @@ __global__ __launch_bounds__(64) void k_particle_events_finish(ParticleEventArgs
 using namespace pilco;
 
 void launch_particle_head(hipStream_t st, const ParticleHeadArgs& a) {
-    hipLaunchKernelGGL(k_particle_head, dim3((a.ldt + 255) / 256), dim3(256), 0, st, a);
+    const size_t lds_bytes = sizeof(double) * particle_head_lds_doubles(a.kind, a.E, a.U, a.Hn);
+    launch_lds<k_particle_head>(dim3((a.ldt + 255) / 256), dim3(256), lds_bytes, st, a);
 }
 void launch_particle_tail(hipStream_t st, const ParticleTailArgs& a) {
     hipLaunchKernelGGL(k_particle_tail, dim3((a.ntc + 255) / 256), dim3(256), 0, st, a);
@@ -265,7 +286,7 @@ extern "C" int pilco_debug_particle_actions(pilco_ctx* ctx, const pilco_policy* 
     if (!s.pred) s.pred = new PredictWork();
     PredictWork& pw = *s.pred;
     const int ldt = round_up(P, 64);
-    std::vector<double> hp((size_t)U * E + 2 * U + 8, 0.0);
+    std::vector<double> hp(particle_par_doubles(E, U, policy_mlp_hidden(ctx, policy)), 0.0);
     ENSURE(pw.pt_x, (size_t)P * E);
     ENSURE(pw.Xt, (size_t)D * ldt);
     ENSURE(pw.pt_par, hp.size());

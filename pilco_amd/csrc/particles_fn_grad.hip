@@ -124,8 +124,8 @@ int rollout_particles_fn_grad(pilco_ctx* ctx, const FnPlan& pl, const pilco_poli
 // the refusals of both entry points, before any launch or upload: those of the marginal gradient, then those of the
 // function-sample rollout about the slot, the draws and the budget
 int check_fn_grad_call(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0, int P,
-                       int H, const double* reward, bool rbf, const pilco_function_draws* draws, FnPlan& pl) {
-    if (int r = check_particle_grad_call(ctx, "rollout_particles_fn_grad", policy, rewards, n_rewards, x0, P, H, reward, rbf)) return r;
+                       int H, const double* reward, int entry, const pilco_function_draws* draws, FnPlan& pl) {
+    if (int r = check_particle_grad_call(ctx, "rollout_particles_fn_grad", policy, rewards, n_rewards, x0, P, H, reward, entry)) return r;
     return fn_plan(ctx, "rollout_particles_fn_grad", draws, P, pl);
 }
 
@@ -138,7 +138,7 @@ extern "C" int pilco_rollout_particles_fn_grad(pilco_ctx* ctx, const pilco_polic
                                                double* dW, double* db, double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
     FnPlan pl{};
-    if (int r = check_fn_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, false, draws, pl)) return r;
+    if (int r = check_fn_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, PILCO_POLICY_LINEAR, draws, pl)) return r;
     return pg_linear_entry(ctx, "rollout_particles_fn_grad", policy, dW, db, [&](std::vector<double>& par) {
         return rollout_particles_fn_grad(ctx, pl, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, draws, draws_out,
                                          reward, reward_steps, par, dreturn_dx0);
@@ -153,8 +153,22 @@ extern "C" int pilco_rollout_particles_fn_grad_rbf(pilco_ctx* ctx, const pilco_p
                                                    double* reward_steps, double* dX, double* dY, double* dls, double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
     FnPlan pl{};
-    if (int r = check_fn_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, true, draws, pl)) return r;
+    if (int r = check_fn_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, PILCO_POLICY_RBF, draws, pl)) return r;
     return pg_rbf_entry(ctx, "rollout_particles_fn_grad", policy, Xp, Yp, lsp, noisep, bf, dX, dY, dls, [&](std::vector<double>& par) {
+        return rollout_particles_fn_grad(ctx, pl, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, draws, draws_out,
+                                         reward, reward_steps, par, dreturn_dx0);
+    });
+}
+
+extern "C" int pilco_rollout_particles_fn_grad_mlp(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards,
+                                                   int n_rewards, const double* x0, int P, int H, const double* eps,
+                                                   unsigned long long seed, int observation_noise, const pilco_function_draws* draws,
+                                                   const pilco_function_draws_out* draws_out, double* reward, double* reward_steps,
+                                                   double* dW1, double* db1, double* dW2, double* db2, double* dreturn_dx0) {
+    if (!ctx) return PILCO_E_SHAPE;
+    FnPlan pl{};
+    if (int r = check_fn_grad_call(ctx, policy, rewards, n_rewards, x0, P, H, reward, PILCO_POLICY_MLP, draws, pl)) return r;
+    return pg_mlp_entry(ctx, "rollout_particles_fn_grad", policy, dW1, db1, dW2, db2, [&](std::vector<double>& par) {
         return rollout_particles_fn_grad(ctx, pl, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, draws, draws_out,
                                          reward, reward_steps, par, dreturn_dx0);
     });

@@ -13,6 +13,9 @@
 //                    (step H - 1 meets lam_H = 0: its matrix is neither computed nor read)
 //   k_pg_param_partials   (t <= H - 2) per block of PT_BLOCK particles and per parameter the block's sum, added to the block's cell
 // and after the last group  k_pg_finish: the blocks' cells in block order, divided by P.
+// An MLP policy (pilco_rollout_particles_grad_mlp; docs/particle_mlp.md) has a branch of its own in the reverse step (compiled
+// into k_pg_reverse_mlp, an instance of k_pg_reverse's body) and in
+// k_pg_param_partials; its hidden units are evaluated by mlp_hidden (particles.h), the statements of k_particle_head, on LDS copies of the parameters.
 // The host side of a call -- plan, buffers, staging, the sweep over the groups, the finish -- is ParticleGradFrame
 // (particle_frame.hip); the driver here passes it the forward launches of one step of a group.
 //
@@ -65,7 +68,10 @@ __global__ __launch_bounds__(64) void k_pg_reward_partials(const double* rew, do
     part[(long)(b0 + b) * H + t] = s;
 }
 
-__global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) {
+// MLP: the instance that holds the MLP policy's branch (k_pg_reverse_mlp).  With the branch inside k_pg_reverse the kernel takes
+// 98 registers and kinds 0-2 lose a wave per SIMD (5 -> 4), so launch_pg_reverse picks the kernel by kind
+template <bool MLP>
+__device__ __forceinline__ void pg_reverse_body(const PgReverseArgs& a) {
     extern __shared__ double pg_lds[];
     const ParticleHeadArgs& po = a.pol;
     const int E = po.E, U = po.U, D = E + U, tid = threadIdx.x, ldg = a.ldg;
@@ -74,8 +80,11 @@ __global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) {
     double* ln = xs + E * PG_RB;
     double* du = ln + E * PG_RB;
     double* il_s = pg_lds + (3 * E + U) * PG_RB;
+    double* sc = il_s + U * E + tid;          // MLP policy: the pre-squash sums, element k: sc[k * PG_RB]; then the parameters
+    const double* mlp_w = il_s + U * E + U * PG_RB;
     if (po.kind == PILCO_POLICY_RBF)
         for (int q = tid; q < U * E; q += PG_RB) il_s[q] = 1.0 / po.pls[q];
+    if (MLP && po.kind == PILCO_POLICY_MLP) mlp_stage(po, il_s + U * E + U * PG_RB, tid, PG_RB);
     __syncthreads();
     const int l = blockIdx.x * PG_RB + tid;
     if (l >= po.ntc) return;
@@ -93,8 +102,31 @@ __global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) {
         for (int e = 0; e < E; ++e) ln[e * PG_RB] = 0.0;
         for (int k = 0; k < U; ++k) du[k * PG_RB] = 0.0;
     }
+    // the MLP policy: ds_k = g_u[k] d u_k / d s_k into du, then delta_j and lam'_e += sum_j W1_je delta_j, j ascending; every
+    // h_j comes from mlp_hidden twice with the same bits (no barrier below: a thread touches its own columns only)
+    if (MLP && po.kind == PILCO_POLICY_MLP) {
+        const int Hn = po.Hn;
+        const double *W1 = mlp_w, *b1 = W1 + Hn * E, *W2 = b1 + Hn, *b2 = W2 + U * Hn;
+        if (po.squash) {
+            for (int k = 0; k < U; ++k) sc[k * PG_RB] = 0.0;
+            for (int j = 0; j < Hn; ++j) {
+                const double h = mlp_hidden(W1 + j * E, b1[j], xs, PG_RB, E);
+                for (int k = 0; k < U; ++k) sc[k * PG_RB] = fma(W2[k * Hn + j], h, sc[k * PG_RB]);
+            }
+            for (int k = 0; k < U; ++k) {
+                const double s = sc[k * PG_RB] + b2[k];
+                du[k * PG_RB] = du[k * PG_RB] * (po.maxact[k] * cos(s));
+            }
+        }
+        for (int j = 0; j < Hn; ++j) {
+            const double dj = mlp_delta(W2 + j, Hn, mlp_hidden(W1 + j * E, b1[j], xs, PG_RB, E), du, PG_RB, U);
+            for (int e = 0; e < E; ++e) ln[e * PG_RB] = fma(W1[j * E + e], dj, ln[e * PG_RB]);
+        }
+        for (int k = 0; k < U; ++k) a.ds[(long)k * ldg + l] = du[k * PG_RB];
+    }
     // the policy: ds_k = g_u[k] d u_k / d s_k, lam' += (ds / dx)^T ds
-    for (int k = 0; k < U; ++k) {
+    const int Uk = (MLP && po.kind == PILCO_POLICY_MLP) ? 0 : U;   // (the MLP policy: done above)
+    for (int k = 0; k < Uk; ++k) {
         const double gu = du[k * PG_RB];
         double dsk = gu;
         if (po.kind == PILCO_POLICY_LINEAR) {
@@ -157,12 +189,16 @@ __global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) {
     for (int e = 0; e < E; ++e) a.lam_out[(long)e * ldg + l] = ln[e * PG_RB];
 }
 
+__global__ __launch_bounds__(PG_RB) void k_pg_reverse(PgReverseArgs a) { pg_reverse_body<false>(a); }
+__global__ __launch_bounds__(PG_RB) void k_pg_reverse_mlp(PgReverseArgs a) { pg_reverse_body<true>(a); }
+
 // block b of the group: particles PT_BLOCK b .. ; thread q adds quantity q over them in index order
 __global__ __launch_bounds__(PT_BLOCK) void k_pg_param_partials(PgParamArgs a) {
     const ParticleHeadArgs& po = a.pol;
     const int E = po.E, U = po.U, Q = a.Q, bf = po.pn;
     __shared__ double sh[PT_BLOCK * MAX_D];        // [particle][x] then [particle][ds]
     __shared__ double il_s[MAX_D * MAX_D / 4];     // RbfController: 1 / lengthscale [U][E]  (U + E <= MAX_D)
+    extern __shared__ double pt_tile[];            // MLP policy: [PT_BLOCK][PG_MLP_TILE + 1] the block's h, then delta, of a tile
     double* xs = sh;
     double* dss = sh + PT_BLOCK * E;
     const int i = threadIdx.x;
@@ -176,6 +212,53 @@ __global__ __launch_bounds__(PT_BLOCK) void k_pg_param_partials(PgParamArgs a) {
         for (int q = i; q < U * E; q += PT_BLOCK) il_s[q] = 1.0 / po.pls[q];
     __syncthreads();
     double* cell = a.part + (long)(po.p0 / PT_BLOCK + blockIdx.x) * Q;
+    // the MLP policy, cells dW1 [Hn][E] | db1 [Hn] | dW2 [U][Hn] | db2 [U]: per tile of hidden units one tanh per (unit,
+    // particle) -- thread i stages particle i's row -- then a thread per quantity over the particles in index order.  Every
+    // thread reaches every barrier (five per tile): the bounds of the tile loop are uniform and nothing returns early
+    if (po.kind == PILCO_POLICY_MLP) {
+        const int Hn = po.Hn, ld = PG_MLP_TILE + 1;
+        double *c_b1 = cell + Hn * E, *c_W2 = c_b1 + Hn, *c_b2 = c_W2 + U * Hn;
+        double *w1 = pt_tile + PT_BLOCK * ld, *b1 = w1 + PG_MLP_TILE * E, *w2 = b1 + PG_MLP_TILE;   // the tile's parameters
+        for (int j0 = 0; j0 < Hn; j0 += PG_MLP_TILE) {
+            const int nj = min(PG_MLP_TILE, Hn - j0);
+            __syncthreads();   // the readers of the tile before
+            for (int q = i; q < nj * E; q += PT_BLOCK) w1[q] = po.W1[j0 * E + q];
+            for (int q = i; q < nj; q += PT_BLOCK) b1[q] = po.b1[j0 + q];
+            for (int q = i; q < U * nj; q += PT_BLOCK) w2[(q / nj) * PG_MLP_TILE + q % nj] = po.W2[(q / nj) * Hn + j0 + q % nj];
+            __syncthreads();
+            if (i < nv)
+                for (int jj = 0; jj < nj; ++jj) pt_tile[i * ld + jj] = mlp_hidden(w1 + jj * E, b1[jj], xs + i * E, 1, E);
+            __syncthreads();
+            for (int q = i; q < U * nj; q += PT_BLOCK) {              // d W2_kj = sum ds_k h_j
+                const int k = q / nj, jj = q - k * nj;
+                double s = 0.0;
+                for (int j = 0; j < nv; ++j) s = fma(dss[j * U + k], pt_tile[j * ld + jj], s);
+                c_W2[k * Hn + j0 + jj] += s;
+            }
+            __syncthreads();
+            if (i < nv)
+                for (int jj = 0; jj < nj; ++jj)
+                    pt_tile[i * ld + jj] = mlp_delta(w2 + jj, PG_MLP_TILE, pt_tile[i * ld + jj], dss + i * U, 1, U);
+            __syncthreads();
+            for (int q = i; q < nj * (E + 1); q += PT_BLOCK) {        // d W1_je = sum delta_j x_e, d b1_j = sum delta_j
+                const int jj = q / (E + 1), e = q - jj * (E + 1);
+                double s = 0.0;
+                if (e < E) {
+                    for (int j = 0; j < nv; ++j) s = fma(pt_tile[j * ld + jj], xs[j * E + e], s);
+                    cell[(j0 + jj) * E + e] += s;
+                } else {
+                    for (int j = 0; j < nv; ++j) s += pt_tile[j * ld + jj];
+                    c_b1[j0 + jj] += s;
+                }
+            }
+        }
+        for (int k = i; k < U; k += PT_BLOCK) {                       // d b2_k = sum ds_k
+            double s = 0.0;
+            for (int j = 0; j < nv; ++j) s += dss[j * U + k];
+            c_b2[k] += s;
+        }
+        return;
+    }
     // k_kc of particle j: the basis function as k_particle_head evaluates it
     auto basis = [&](int j, int k, int c) {
         double r2 = 0.0;
@@ -247,12 +330,15 @@ void launch_pg_reward_partials(hipStream_t st, const double* rew, double* part, 
 }
 
 void launch_pg_reverse(hipStream_t st, const PgReverseArgs& a) {
-    const int lds_bytes = (int)sizeof(double) * pg_reverse_lds_doubles(a.pol.E, a.pol.U);
-    hipLaunchKernelGGL(k_pg_reverse, dim3((a.pol.ntc + PG_RB - 1) / PG_RB), dim3(PG_RB), lds_bytes, st, a);
+    const int lds_bytes = (int)sizeof(double) * pg_reverse_lds_doubles(a.pol.E, a.pol.U, a.pol.kind, a.pol.Hn);
+    const dim3 grid((a.pol.ntc + PG_RB - 1) / PG_RB);
+    if (a.pol.kind == PILCO_POLICY_MLP) launch_lds<k_pg_reverse_mlp>(grid, dim3(PG_RB), lds_bytes, st, a);
+    else launch_lds<k_pg_reverse>(grid, dim3(PG_RB), lds_bytes, st, a);
 }
 
 void launch_pg_param_partials(hipStream_t st, const PgParamArgs& a) {
-    hipLaunchKernelGGL(k_pg_param_partials, dim3((a.pol.ntc + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, st, a);
+    const size_t lds_bytes = sizeof(double) * pg_param_lds_doubles(a.pol.kind, a.pol.E, a.pol.U);
+    launch_lds<k_pg_param_partials>(dim3((a.pol.ntc + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), lds_bytes, st, a);
 }
 
 void launch_pg_finish(hipStream_t st, const double* part, double* out, int nblk, int Q, int P) {
@@ -261,7 +347,8 @@ void launch_pg_finish(hipStream_t st, const double* part, double* out, int nblk,
 
 namespace {
 
-// Both entry points.  par: LinearController dW (U,E) | db (U); RbfController dbeta (U,bf) | dC (bf,E) | dl (U,E), over P.
+// The three entry points.  par: LinearController dW (U,E) | db (U); RbfController dbeta (U,bf) | dC (bf,E) | dl (U,E); MLP policy
+// dW1 (Hn,E) | db1 (Hn) | dW2 (U,Hn) | db2 (U), over P.
 // The frame (particle_frame.hip) holds what surrounds the forward pass
 int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0,
                            int P, int H, const double* eps, unsigned long long seed, int observation_noise, double* reward,
@@ -333,13 +420,13 @@ int rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* policy, const pil
 
 // the refusals of both entry points, before any launch or upload
 int check_particle_grad_call(pilco_ctx* ctx, const char* who, const pilco_policy* policy, const pilco_reward_term* rewards, int n_rewards, const double* x0, int P,
-                    int H, const double* reward, bool rbf) {
+                    int H, const double* reward, int entry) {
     if (int r = check_particle_state(ctx, P, H)) return r;
     if (!x0 || !reward) return fail(ctx, PILCO_E_SHAPE, std::string(who) + ": null x0 or reward");
     if (int r = check_particle_terms(ctx, policy, rewards, n_rewards)) return r;
-    if (rbf != (policy->kind == PILCO_POLICY_RBF))
+    if (entry != (policy->kind == PILCO_POLICY_NONE ? PILCO_POLICY_LINEAR : policy->kind))
         return fail(ctx, PILCO_E_SHAPE, std::string(who) + ": no policy or a LinearController (pilco_" + who + "), an "
-                                        "RbfController (pilco_" + who + "_rbf)");
+                                        "RbfController (pilco_" + who + "_rbf), an MLP policy (pilco_" + who + "_mlp)");
     return PILCO_OK;
 }
 
@@ -348,7 +435,7 @@ extern "C" int pilco_rollout_particles_grad(pilco_ctx* ctx, const pilco_policy* 
                                             int observation_noise, double* reward, double* reward_steps, double* dW, double* db,
                                             double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
-    if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, false)) return r;
+    if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, PILCO_POLICY_LINEAR)) return r;
     return pg_linear_entry(ctx, "rollout_particles_grad", policy, dW, db, [&](std::vector<double>& par) {
         return rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
                                       dreturn_dx0);
@@ -361,8 +448,20 @@ extern "C" int pilco_rollout_particles_grad_rbf(pilco_ctx* ctx, const pilco_poli
                                                 const double* lsp, const double* noisep, int bf, double* reward, double* reward_steps,
                                                 double* dX, double* dY, double* dls, double* dreturn_dx0) {
     if (!ctx) return PILCO_E_SHAPE;
-    if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, true)) return r;
+    if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, PILCO_POLICY_RBF)) return r;
     return pg_rbf_entry(ctx, "rollout_particles_grad", policy, Xp, Yp, lsp, noisep, bf, dX, dY, dls, [&](std::vector<double>& par) {
+        return rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
+                                      dreturn_dx0);
+    });
+}
+
+extern "C" int pilco_rollout_particles_grad_mlp(pilco_ctx* ctx, const pilco_policy* policy, const pilco_reward_term* rewards,
+                                                int n_rewards, const double* x0, int P, int H, const double* eps,
+                                                unsigned long long seed, int observation_noise, double* reward, double* reward_steps,
+                                                double* dW1, double* db1, double* dW2, double* db2, double* dreturn_dx0) {
+    if (!ctx) return PILCO_E_SHAPE;
+    if (int r = check_particle_grad_call(ctx, "rollout_particles_grad", policy, rewards, n_rewards, x0, P, H, reward, PILCO_POLICY_MLP)) return r;
+    return pg_mlp_entry(ctx, "rollout_particles_grad", policy, dW1, db1, dW2, db2, [&](std::vector<double>& par) {
         return rollout_particles_grad(ctx, policy, rewards, n_rewards, x0, P, H, eps, seed, observation_noise, reward, reward_steps, par,
                                       dreturn_dx0);
     });

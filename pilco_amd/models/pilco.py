@@ -158,8 +158,16 @@ class PILCO:
                 seeds[t, E:] += c * np.ravel(ds)
         return value, seeds
 
+    def _refuse_mlp(self, who):
+        """a network policy has no action moments: the moment-matching methods refuse it before any device call"""
+        if self.control_dim > 0 and isinstance(self.controller, controllers.MlpController):
+            raise NotImplementedError("%s: moment matching needs the action's moments in closed form, which an MlpController "
+                                      "does not have; use the particle paths (sample_trajectories, particle_value_and_gradient, "
+                                      "optimize_policy(objective=\"particles\"))" % who)
+
     # pilco.py:47-50
     def training_loss(self):
+        self._refuse_mlp("training_loss")
         return -self.predict(self.m_init, self.S_init, self.horizon)[2]
 
     # pilco.py:52-73 (the pandas pretty-printing is cosmetic and omitted)
@@ -175,7 +183,8 @@ class PILCO:
     # pilco.py:75-113
     def optimize_policy(self, maxiter=50, restarts=1, verbose=True, objective="moment_matching", particle_options=None):
         """objective="particles" (extension): maximise the particle return of particle_value_and_gradient on fixed initial
-        particles and draws instead of the moment-matched reward; particle_options: num_particles, seed, observation_noise."""
+        particles and draws instead of the moment-matched reward; particle_options: num_particles, seed, observation_noise.
+        An MlpController is optimised with objective="particles" only: the default objective raises NotImplementedError."""
         from ..training import optimize_policy
         return optimize_policy(self, maxiter=maxiter, restarts=restarts, verbose=verbose, objective=objective,
                                particle_options=particle_options)
@@ -188,6 +197,7 @@ class PILCO:
         pilco_rollout_grad_rbf) and deterministic: the same inputs give bitwise the same gradient.
         seed_fn(traj (H+1, E+E*E)) -> cotangent seeds d objective / d (m_t, s_t) for an objective beyond the additive
         reward (the returned reward is the additive part; the gradients are those of additive reward + seeded objective)."""
+        self._refuse_mlp("value_and_gradient")
         ctl = self.controller
         linear = isinstance(ctl, controllers.LinearController)
         if not linear and not isinstance(ctl, controllers.RbfController):
@@ -227,7 +237,8 @@ class PILCO:
         """Extension: (reward, grads) of the PARTICLE return -- sample_trajectories(...).reward_steps.sum() on the same initial
         particles and draws -- w.r.t. the controller parameters, on the device (pilco_rollout_particles_grad / _grad_rbf;
         docs/particle_gradients.md).  grads has the structure value_and_gradient returns: (dW, db) for a LinearController,
-        (dX, dY, dlengthscales) for an RbfController, () without a controller.  m_x, s_x, n default to m_init, S_init and
+        (dX, dY, dlengthscales) for an RbfController, (dW1, db1, dW2, db2) in the parameters' shapes for an MlpController
+        (pilco_rollout_particles_grad_mlp / _fn_grad_mlp; docs/particle_mlp.md), () without a controller.  m_x, s_x, n default to m_init, S_init and
         horizon; x0, eps, seed and observation_noise are those of sample_trajectories.  With x0 (or seed) and the draws fixed
         the value is a deterministic, smooth function of the parameters (common random numbers).  return_dx0: a third
         result (P, E), row p the gradient of particle p's own return w.r.t. its initial state.  Any reward term evaluated on
@@ -241,8 +252,9 @@ class PILCO:
                                       "part of the differentiated objective")
         ctl = self.controller if self.control_dim > 0 else None
         linear = isinstance(ctl, controllers.LinearController)
-        if ctl is not None and not linear and not isinstance(ctl, controllers.RbfController):
-            raise TypeError("particle policy gradient: LinearController or RbfController")
+        mlp = isinstance(ctl, controllers.MlpController)
+        if ctl is not None and not linear and not mlp and not isinstance(ctl, controllers.RbfController):
+            raise TypeError("particle policy gradient: LinearController, RbfController or MlpController")
         m_x = self.m_init if m_x is None else m_x
         s_x = self.S_init if s_x is None else s_x
         n = self.horizon if n is None else int(n)
@@ -256,13 +268,19 @@ class PILCO:
             if function_draws is not None:
                 function_draws = {k: function_draws[k] for k in ("omega", "phase", "w", "xi")}
             kw.update(num_features=num_features, function_draws=function_draws)
-            if ctl is None or linear:
+            if mlp:
+                r, _, *g, dx0, _ = self.ctx.rollout_particles_fn_grad_mlp(self._policy_spec(), self._reward_terms(), x0, n, **kw)
+                grads = tuple(a.reshape(p.shape) for a, p in zip(g, (ctl.W1, ctl.b1, ctl.W2, ctl.b2)))
+            elif ctl is None or linear:
                 r, _, dW, db, dx0, _ = self.ctx.rollout_particles_fn_grad(self._policy_spec(), self._reward_terms(), x0, n, **kw)
                 grads = (dW.reshape(ctl.W.shape), db.reshape(ctl.b.shape)) if linear else ()
             else:
                 r, _, dX, dY, dl, dx0, _ = self.ctx.rollout_particles_fn_grad_rbf(self._policy_spec(), self._reward_terms(), x0, n,
                                                                                   ctl.X, ctl.Y, ctl.lengthscales, ctl.noise, **kw)
                 grads = (dX, dY, dl)
+        elif mlp:
+            r, _, *g, dx0 = self.ctx.rollout_particles_grad_mlp(self._policy_spec(), self._reward_terms(), x0, n, **kw)
+            grads = tuple(a.reshape(p.shape) for a, p in zip(g, (ctl.W1, ctl.b1, ctl.W2, ctl.b2)))
         elif ctl is None or linear:
             r, _, dW, db, dx0 = self.ctx.rollout_particles_grad(self._policy_spec(), self._reward_terms(), x0, n, **kw)
             grads = (dW.reshape(ctl.W.shape), db.reshape(ctl.b.shape)) if linear else ()
@@ -314,6 +332,7 @@ class PILCO:
 
     # pilco.py:118-136
     def predict(self, m_x, s_x, n):
+        self._refuse_mlp("predict")
         self.mgpr._user_factors = None
         self.mgpr._ensure_factorized()
         if not self._host_reward_terms():
@@ -323,6 +342,7 @@ class PILCO:
 
     def predict_trajectory(self, m_x, s_x, n):
         """Extension: also returns the (n+1, E + E*E) per-step states."""
+        self._refuse_mlp("predict_trajectory")
         self.mgpr._user_factors = None
         self.mgpr._ensure_factorized()
         M, S, R, traj = self.ctx.rollout(self._policy_spec(), self._reward_terms(), m_x, s_x, int(n), want_traj=True)
@@ -426,12 +446,14 @@ class PILCO:
 
     # pilco.py:138-153
     def propagate(self, m_x, s_x):
+        self._refuse_mlp("propagate")
         self.mgpr._user_factors = None
         self.mgpr._ensure_factorized()
         return self.ctx.propagate(self._policy_spec(), m_x, s_x)
 
     # pilco.py:155-156
     def compute_reward(self):
+        self._refuse_mlp("compute_reward")
         return -self.training_loss()
 
     @property

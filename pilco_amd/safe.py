@@ -130,8 +130,9 @@ class RiskSample:
         self.__dict__.update(fields)
 
     def __repr__(self):
-        return "RiskSample(steps=%d, any_hit_particles=%.6g, any_hit_moment_matched=%.6g)" % (
-            self.risk_particles.shape[0], self.any_hit_particles, self.any_hit_moment_matched)
+        mm = self.any_hit_moment_matched   # (None with an MlpController: no moment-matched side)
+        return "RiskSample(steps=%d, any_hit_particles=%.6g, any_hit_moment_matched=%s)" % (
+            self.risk_particles.shape[0], self.any_hit_particles, "None" if mm is None else "%.6g" % mm)
 
 
 class SafePILCO(PILCO):
@@ -160,7 +161,8 @@ class SafePILCO(PILCO):
         (sample_trajectories with reward_mult's event; docs/particles.md).  kwargs go to sample_trajectories (eps, x0,
         observation_noise, return_particles, jitter, eps_obs); dynamics ("marginal", "function" or "conditioned") and
         num_features are sample_trajectories' own (docs/particle_functions.md, docs/particle_conditioned.md).  Returns a
-        RiskSample.  risk_moment_matched follows the reference (the variance entry as the Normal scale, the steps independent in any_hit_moment_matched): it need not agree with the particles."""
+        RiskSample.  With an MlpController (docs/particle_mlp.md) there is no moment-matched side: risk_moment_matched,
+        any_hit_moment_matched and objective_moment_matched are None.  risk_moment_matched follows the reference (the variance entry as the Normal scale, the steps independent in any_hit_moment_matched): it need not agree with the particles."""
         if not hasattr(self.reward_mult, "event_spec"):
             raise TypeError("sample_risk: reward_mult offers no event_spec()")
         n, E = int(n), self.state_dim
@@ -168,11 +170,16 @@ class SafePILCO(PILCO):
             kwargs["num_features"] = num_features
         res = self.sample_trajectories(m_x, s_x, n, num_particles=num_particles, seed=seed, events=[self.reward_mult], dynamics=dynamics,
                                        **kwargs)
+        first = res.first_hit[:, 0]
+        any_p = np.count_nonzero((first >= 0) & (first < n)) / first.shape[0]
+        from .controllers import MlpController
+        if self.control_dim > 0 and isinstance(self.controller, MlpController):
+            return RiskSample(risk_particles=res.event_prob[:n, 0].copy(), risk_moment_matched=None, any_hit_particles=any_p,
+                              any_hit_moment_matched=None, objective_particles=float(res.reward_steps.sum()) + self._mu() * any_p,
+                              objective_moment_matched=None, trajectories=res)
         traj = self.predict_trajectory(m_x, s_x, n)[3]
         risk_mm = np.array([float(np.ravel(self.reward_mult.compute_reward(traj[t, :E].reshape(1, E), traj[t, E:].reshape(E, E))[0])[0])
                             for t in range(n)], np.float64).reshape(n)
-        first = res.first_hit[:, 0]
-        any_p = np.count_nonzero((first >= 0) & (first < n)) / first.shape[0]
         return RiskSample(risk_particles=res.event_prob[:n, 0].copy(), risk_moment_matched=risk_mm, any_hit_particles=any_p,
                           any_hit_moment_matched=1.0 - float(np.prod(1.0 - risk_mm)),
                           objective_particles=float(res.reward_steps.sum()) + self._mu() * any_p,

@@ -382,8 +382,21 @@ def optimize_smgpr(smgpr, restarts=1, maxiter=None, keep="last"):
 
 # --------------------------------------------------------------------------- policy
 def _policy_params(controller):
-    """(get, set) over a flat unconstrained vector for LinearController / RbfController."""
-    from .controllers import LinearController, RbfController
+    """(get, set) over a flat unconstrained vector for LinearController / RbfController / MlpController."""
+    from .controllers import LinearController, MlpController, RbfController
+    if isinstance(controller, MlpController):
+        ps = [controller.W1, controller.b1, controller.W2, controller.b2]
+
+        def get():
+            return np.concatenate([np.asarray(p.numpy(), np.float64).ravel() for p in ps])
+
+        def put(u):
+            o = 0
+            for p in ps:
+                n = int(np.prod(p.shape))
+                p.assign(u[o:o + n].reshape(p.shape))
+                o += n
+        return get, put
     if isinstance(controller, LinearController):
         shapes = [controller.W.shape, controller.b.shape]
 
@@ -411,7 +424,7 @@ def _policy_params(controller):
             for i, m in enumerate(gp.models):
                 m.kernel.lengthscales.assign(ls[i])
         return get, put
-    raise TypeError("optimize_policy supports LinearController and RbfController")
+    raise TypeError("optimize_policy supports LinearController, RbfController and MlpController")
 
 
 def policy_loss_and_grad(pilco, u, put, eps=1e-6):
@@ -598,10 +611,12 @@ def _optimize_policy_lanes(pilco, maxiter, restarts, verbose, seeded=False):
 def particle_loss_and_grad(pilco, u, put, x0, seed, observation_noise, dynamics="marginal", num_features=512):
     """-J and its gradient for the particle return on the fixed initial particles x0 and the draws of `seed`
     (PILCO.particle_value_and_gradient)."""
-    from .controllers import LinearController
+    from .controllers import LinearController, MlpController
     put(u)
     r, grads = pilco.particle_value_and_gradient(x0=x0, seed=seed, observation_noise=observation_noise, dynamics=dynamics,
                                                  num_features=num_features)
+    if isinstance(pilco.controller, MlpController):                # [W1, b1, W2, b2], unconstrained
+        return -r, -np.concatenate([g.ravel() for g in grads])
     if isinstance(pilco.controller, LinearController):
         Wb, bb = grads
         return -r, -np.concatenate([Wb.ravel(), bb.ravel()])
@@ -616,13 +631,16 @@ def optimize_policy(pilco, maxiter=50, restarts=1, verbose=True, objective="mome
     are fixed over the whole walk and over the restarts, so the objective is deterministic and smooth); the restarts run one
     after the other and are compared by their particle return.  particle_options: num_particles (1000), seed (0),
     observation_noise (False), dynamics ("marginal"; "function": the return over posterior function samples,
-    docs/particle_fn_gradients.md) and num_features (512, with dynamics="function").  The function draws are those of `seed`,
+    docs/particle_fn_gradients.md) and num_features (512, with dynamics="function").  An MlpController (docs/particle_mlp.md)
+    is optimised with objective="particles" only; the default objective raises NotImplementedError.  The function draws are those of `seed`,
     generated on the device at every evaluation: the same functions over the walk and over the restarts, like x0."""
     if objective not in ("moment_matching", "particles"):
         raise ValueError("optimize_policy: objective is 'moment_matching' or 'particles'")
     if pilco.controller is None:
         raise ValueError("optimize_policy: the model has no controller (control_dim == 0)")
     particles = objective == "particles"
+    if not particles:
+        pilco._refuse_mlp("optimize_policy(objective=\"moment_matching\")")
     if particles:
         opts = dict(num_particles=1000, seed=0, observation_noise=False, dynamics="marginal", num_features=512)
         unknown = set(particle_options or {}) - set(opts)
